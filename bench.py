@@ -1,7 +1,14 @@
 """Benchmark: batched ShippingEnv step on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n ENVS_PER_GPU]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n ENVS_PER_GPU] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline figure needs and nothing else: it sets the config-3
+workload up (reset, pre-roll), warms up W steps, times K steps, writes the last timed step's
+outputs if --dump-outputs is given, and prints the line. --full adds every other leg to the
+same line: config 3 from reset, with one Python call per step and to the survey's letter,
+config 4, config 1, the rollouts, config 5, the DQN training loop, the 2^24 runs and the CPU
+baseline (the legs' own options below apply under --full only).
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py launches its own N
 ranks (spawn_ranks: N fresh child processes, one per GPU, RANK / LOCAL_RANK /
@@ -15,7 +22,7 @@ default ports, synthetic agent actions (90 % move, 5 % take cargo, 3 % take
 fuel, 2 % select; Philox-generated, resident in HBM before timing). Config 4
 (64 random ports, auto-reset with ballot-compacted done list and per-wave
 episode-return reduction, RCCL all-reduce of the stats) is measured in the same
-run and reported under "config4". Weak scaling: every rank owns 2^20 envs with
+run under --full and reported under "config4". Weak scaling: every rank owns 2^20 envs with
 global ids rank*2^20 + i.
 
 Rank 0 prints ONE JSON line on stdout; progress goes to stderr.
@@ -61,6 +68,12 @@ def parse():
     p.add_argument("--warmup", type=int, default=50)
     p.add_argument("--n", type=int, default=1 << 20, help="envs per GPU")
     p.add_argument("--seed", type=int, default=2026)
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beside the headline (config 3 from reset, step_py and literal, "
+                        "config 4, config 1, rollouts, config 5, DQN training, large N, the CPU baseline)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the headline leg's last timed step left "
+                        "(DUMP_FIELDS) as DIR/<name>.npy, float32 / float64")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget")
     p.add_argument("--no-cpu", action="store_true")
     p.add_argument("--no-config4", action="store_true")
@@ -200,11 +213,57 @@ def spawn_ranks(n, argv, script=None, env=None, grace_s=30.0):
     return 0
 
 
+ACTION_TABLE_BYTES = 16 << 30  # the resident action rows: 4096 rows of 2^20 int32
+
+
 def make_actions(env, steps):
-    acts = torch.empty((steps, env.n), dtype=torch.int32, device=env.device)
-    for t in range(steps):
+    """Rows t = 0 .. steps - 1 of the synthetic agent's actions, resident in HBM. A run of
+    more steps than ACTION_TABLE_BYTES holds rows for takes them round the table again, so
+    --steps is bounded by time, not by memory."""
+    rows = max(1, min(steps, ACTION_TABLE_BYTES // (4 * max(env.n, 1))))
+    acts = torch.empty((rows, env.n), dtype=torch.int32, device=env.device)
+    for t in range(rows):
         env.gen_actions(t, out=acts[t])
     return acts
+
+
+# --dump-outputs: what VecEnv.step / step_seq return (reward, done, err) and the state they
+# leave, after the last timed step; integers that float32 holds exactly go as float32
+DUMP_FIELDS = (("reward", "float32"), ("done", "float32"), ("err", "float32"), ("x", "float32"),
+               ("y", "float32"), ("origin", "float32"), ("dest", "float32"), ("cargo", "float64"),
+               ("fuel", "float64"))
+DUMP_BYTES = 64_000_000  # over all files and ranks
+DUMP_SAMPLE_SEED = 20260
+
+
+def dump_sample(n, world=1):
+    """None if every env's DUMP_FIELDS fit DUMP_BYTES / world, else the sorted env indices of
+    a fixed seeded sample that does (they are written too, as env_index.npy)."""
+    import numpy as np
+
+    per_env = sum(np.dtype(t).itemsize for _, t in DUMP_FIELDS)
+    budget = DUMP_BYTES // world
+    if n * per_env <= budget:
+        return None
+    m = budget // (per_env + 8)
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=m, replace=False))
+
+
+def dump_outputs(env, path, rank=0, world=1):
+    """Write the env's DUMP_FIELDS to path/<name>.npy (rank r > 0: <name>_rank<r>.npy)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    idx = dump_sample(env.n, world)
+    sel = None if idx is None else torch.from_numpy(idx).to(env.device)
+    suffix = f"_rank{rank}" if rank else ""
+    for name, dtype in DUMP_FIELDS:
+        t = getattr(env, name)
+        a = (t if sel is None else t[sel]).cpu().numpy().astype(dtype)
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
+    if idx is not None:
+        np.save(os.path.join(path, f"env_index{suffix}.npy"), idx.astype("float64"))
 
 
 def timed_loop(env, acts, first, steps, dist, reduce_every=0, counter=None, step_seq=False):
@@ -228,15 +287,17 @@ def timed_loop(env, acts, first, steps, dist, reduce_every=0, counter=None, step
     # the step's action rows as views made before the clock starts: indexing the
     # [steps, n] table inside the loop is harness work (1.4 us of host time per step,
     # tools/archive/diag/host_step_cost.py), not the step's
+    rows = acts.shape[0]  # step k takes row (first + k) % rows (make_actions)
     if not step_seq:
-        chunks = [acts[first + k] for k in range(steps)]
-    else:  # runs that end where an all-reduce follows; the first run records ef right before
+        chunks = [acts[(first + k) % rows] for k in range(steps)]
+    else:  # runs that end where an all-reduce follows or the table wraps; the first run records ef right before
         # its launch 1 from native code (se_step_seq_mark, mark_after = 0): splitting the run
         # after launch 1 for a Python record cost ~0.7 us per step over the driver's 20, and a
         # native record there 0.2-0.4 (tools/archive/diag/wall_forms.py, profiles/r04/wall_forms*)
         cuts = sorted({0, steps} | ({k for k in range(reduce_every, steps, reduce_every)}
-                                    if reduce_every else set()))
-        chunks = [acts[first + a:first + b] for a, b in zip(cuts, cuts[1:])]
+                                    if reduce_every else set())
+                      | set(range(rows - first % rows, steps, rows)))
+        chunks = [acts[(first + a) % rows:(first + a) % rows + b - a] for a, b in zip(cuts, cuts[1:])]
     dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -268,11 +329,12 @@ def timed_loop(env, acts, first, steps, dist, reduce_every=0, counter=None, step
     return wall, k_ms
 
 
-def run_config(n, ports, auto, args, dist, label, preroll=0, step_seq=False):
+def run_config(n, ports, auto, args, dist, label, preroll=0, step_seq=False, dump=None):
     """One leg: reset, `preroll` untimed steps of workload setup (actions generated one row
     at a time), W warm-up steps, then the K timed steps from rows resident in HBM.
     Auto-reset legs all-reduce the episode statistics (RCCL) every min(100, K // 2) steps
-    inside the timed region; the count is returned in `info`."""
+    inside the timed region; the count is returned in `info`. dump: a directory for what the
+    last timed step left (dump_outputs), written after the clock stops."""
     from shippingenv_amd.vec import VecEnv
 
     env = VecEnv(n, seed=args.seed, ports=ports, env_id_base=dist.rank * n, device=dist.dev,
@@ -287,10 +349,11 @@ def run_config(n, ports, auto, args, dist, label, preroll=0, step_seq=False):
         for t in range(preroll):  # action rows of their own (t offset past the timed rows)
             env.step(env.gen_actions(1_000_000 + t, out=row))
     for k in range(args.warmup):  # the timed leg's own issue path (and kernel) warmed up
+        r = k % acts.shape[0]
         if step_seq:
-            env.step_seq(acts[k:k + 1])
+            env.step_seq(acts[r:r + 1])
         else:
-            env.step(acts[k])
+            env.step(acts[r])
     if auto:  # the stats path runs inside the timed region: load its kernels now
         dist.D.reduce_episode_stats(env.episode_stats().clone())
     torch.cuda.synchronize()
@@ -305,6 +368,8 @@ def run_config(n, ports, auto, args, dist, label, preroll=0, step_seq=False):
         s = env.episode_stats().clone()
         dist.D.reduce_episode_stats(s)
         stats = s.cpu().tolist()
+    if dump:
+        dump_outputs(env, dump, dist.rank, dist.world)
     env.close()
     del acts
     torch.cuda.empty_cache()
@@ -839,15 +904,12 @@ def main():
     # state mix; DESIGN.md section 5, "The short run"), then the headline leg in steady
     # state, its K steps issued by VecEnv.step_seq (the native launch loop, whose kernel has
     # a trace name of its own), then the same steady leg with one VecEnv.step call per step
-    el3r, k3r, _, _ = run_config(n, None, False, args, dist, "config3-from-reset", preroll=0)
+    # (a plain run times the headline leg alone; the legs around it are --full's)
+    if args.full:
+        el3r, k3r, _, _ = run_config(n, None, False, args, dist, "config3-from-reset", preroll=0)
     el3, k3, _, info3 = run_config(n, None, False, args, dist, "config3", preroll=args.preroll3,
-                                   step_seq=True)
+                                   step_seq=True, dump=args.dump_outputs)
     value = n * dist.world * args.steps / el3
-    el3p, k3p, _, _ = run_config(n, None, False, args, dist, "config3-step-py", preroll=args.preroll3)
-    # SURVEY 8(d) config 3 to the letter: se_reset, warm-up 10, time 1000 steps (whatever K is)
-    lit = argparse.Namespace(**vars(args))
-    lit.steps, lit.warmup = LITERAL_STEPS, LITERAL_WARMUP
-    el3l, k3l, _, _ = run_config(n, None, False, lit, dist, "config3-literal", preroll=0, step_seq=True)
     out = {
         "metric": "env-steps/sec at N=2^20 parallel envs per GPU (config 3: full step, 5 default ports; "
                   "K steps in the steady state after a 1000-step pre-roll; config3_literal: the survey's "
@@ -878,30 +940,46 @@ def main():
             "parallelism": f"env-shard dp{dist.world} (no data-path collective)",
         },
         "roofline": roofline(BYTES_STEP, n, k3, CANONICAL_STEP),
-        "from_reset": {"value": round(n * dist.world * args.steps / el3r, 1),
-                       "ms_per_step": round(el3r / args.steps * 1e3, 5),
-                       "kernel_ms": round(k3r, 5),
-                       "frac": roofline(BYTES_STEP, n, k3r, CANONICAL_STEP)["frac"]},
-        "step_py": {"value": round(n * dist.world * args.steps / el3p, 1),
-                    "ms_per_step": round(el3p / args.steps * 1e3, 5),
-                    "kernel_ms": round(k3p, 5),
-                    "frac": roofline(BYTES_STEP, n, k3p, CANONICAL_STEP)["frac"]},
-        "config3_literal": {"workload": f"SURVEY 8(d) config 3 as written: se_reset, warm-up {LITERAL_WARMUP}, "
-                                        f"{LITERAL_STEPS} timed steps (VecEnv.step_seq), N=2^20 envs/GPU",
-                            "steps": LITERAL_STEPS, "warmup": LITERAL_WARMUP,
-                            "value": round(n * dist.world * LITERAL_STEPS / el3l, 1),
-                            "ms_per_step": round(el3l / LITERAL_STEPS * 1e3, 5),
-                            "kernel_ms": round(k3l, 5),
-                            "frac": roofline(BYTES_STEP, n, k3l, CANONICAL_STEP)["frac"]},
+        "full": args.full,
         "dist": dist.info,
     }
-    for key, obj in (("config3", out["roofline"]), ("config3_from_reset", out["from_reset"]),
-                     ("config3_step_py", out["step_py"]), ("config3_literal", out["config3_literal"])):
-        obj["committed_trace"] = committed_trace(key)
+    out["roofline"]["committed_trace"] = committed_trace("config3")
     traffic, src = pmc_traffic()
     if traffic:
         out["roofline"]["traffic"] = traffic
         out["roofline"]["traffic_source"] = src
+    if args.dump_outputs:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "fields": [name for name, _ in DUMP_FIELDS],
+                               "sampled": dump_sample(n, dist.world) is not None}
+    if not args.full:
+        if dist.rank == 0:
+            print(json.dumps(out), flush=True)
+        dist.close()
+        return
+
+    el3p, k3p, _, _ = run_config(n, None, False, args, dist, "config3-step-py", preroll=args.preroll3)
+    # SURVEY 8(d) config 3 to the letter: se_reset, warm-up 10, time 1000 steps (whatever K is)
+    lit = argparse.Namespace(**vars(args))
+    lit.steps, lit.warmup = LITERAL_STEPS, LITERAL_WARMUP
+    el3l, k3l, _, _ = run_config(n, None, False, lit, dist, "config3-literal", preroll=0, step_seq=True)
+    out["from_reset"] = {"value": round(n * dist.world * args.steps / el3r, 1),
+                         "ms_per_step": round(el3r / args.steps * 1e3, 5),
+                         "kernel_ms": round(k3r, 5),
+                         "frac": roofline(BYTES_STEP, n, k3r, CANONICAL_STEP)["frac"]}
+    out["step_py"] = {"value": round(n * dist.world * args.steps / el3p, 1),
+                      "ms_per_step": round(el3p / args.steps * 1e3, 5),
+                      "kernel_ms": round(k3p, 5),
+                      "frac": roofline(BYTES_STEP, n, k3p, CANONICAL_STEP)["frac"]}
+    out["config3_literal"] = {"workload": f"SURVEY 8(d) config 3 as written: se_reset, warm-up {LITERAL_WARMUP}, "
+                                          f"{LITERAL_STEPS} timed steps (VecEnv.step_seq), N=2^20 envs/GPU",
+                              "steps": LITERAL_STEPS, "warmup": LITERAL_WARMUP,
+                              "value": round(n * dist.world * LITERAL_STEPS / el3l, 1),
+                              "ms_per_step": round(el3l / LITERAL_STEPS * 1e3, 5),
+                              "kernel_ms": round(k3l, 5),
+                              "frac": roofline(BYTES_STEP, n, k3l, CANONICAL_STEP)["frac"]}
+    for key, obj in (("config3_from_reset", out["from_reset"]), ("config3_step_py", out["step_py"]),
+                     ("config3_literal", out["config3_literal"])):
+        obj["committed_trace"] = committed_trace(key)
 
     if not args.no_config4:
         ports64 = random_water_ports(builtin_water(), 64, seed=3)

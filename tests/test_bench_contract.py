@@ -58,6 +58,55 @@ def test_committed_trace_is_labelled_as_such():
     assert "rocprof" not in b.KERNEL_MS_BASIS and "this run" in b.KERNEL_MS_BASIS
 
 
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    import sys
+
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_sample_is_fixed_and_fits_the_budget():
+    """--dump-outputs writes every env while the fields fit 64 MB over all ranks, else the same
+    seeded sample of envs in every run, its indices beside it."""
+    import numpy as np
+
+    b = _bench()
+    per_env = sum(np.dtype(t).itemsize for _, t in b.DUMP_FIELDS)
+    assert all(t in ("float32", "float64") for _, t in b.DUMP_FIELDS)
+    assert b.DUMP_BYTES <= 64_000_000
+    assert b.dump_sample(1 << 20) is None and (1 << 20) * per_env <= b.DUMP_BYTES
+    for n, world in ((1 << 24, 1), (1 << 20, 8)):
+        idx = b.dump_sample(n, world)
+        assert idx is not None and len(idx) * (per_env + 8) * world <= b.DUMP_BYTES
+        assert len(idx) * (per_env + 8) * world > b.DUMP_BYTES * 0.99  # as large as the budget lets it be
+        assert idx.min() >= 0 and idx.max() < n and np.all(np.diff(idx) > 0)
+        assert np.array_equal(idx, b.dump_sample(n, world))
+
+
+def test_action_table_is_bounded_and_wraps(monkeypatch):
+    """make_actions holds at most ACTION_TABLE_BYTES of rows, row t the agent's actions of step t."""
+    import torch
+
+    b = _bench()
+
+    class Env:
+        n, device = 8, torch.device("cpu")
+
+        def gen_actions(self, t, out):
+            out.fill_(t)
+
+    assert b.ACTION_TABLE_BYTES // (4 << 20) >= 1050  # the default 1000 + 50 steps at 2^20 envs: no wrap
+    assert b.make_actions(Env(), 30).shape == (30, 8)
+    monkeypatch.setattr(b, "ACTION_TABLE_BYTES", 5 * 8 * 4)
+    acts = b.make_actions(Env(), 30)
+    assert acts.shape == (5, 8) and acts[:, 0].tolist() == [0, 1, 2, 3, 4]
+
+
 CHILD = r'''
 import json, os, sys, time
 rank = int(os.environ["RANK"])

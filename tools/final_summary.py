@@ -94,7 +94,7 @@ def main():
     kt = json.load(open(os.path.join(dst, "kt_legs.json")))
     legs = {"source": os.path.relpath(os.path.join(dst, "kt_legs.json"), ROOT),
             "trace": f"gpurun_out/{a.tag}/kt_drv_kernel_trace.csv (rocprofv3 --kernel-trace --stats of "
-                     f"bench.py --gpus 1 --steps 20 --warmup 5, tools/gpu_final.sh {a.tag}); kernel averages "
+                     f"bench.py --gpus 1 --steps 20 --warmup 5 --full, tools/gpu_final.sh {a.tag}); kernel averages "
                      f"per name in {os.path.relpath(dst, ROOT)}/kt_drv_kernel_stats.csv",
             "traced_code": f"commit {a.commit}, traced {datetime.date.today().isoformat()}"}
     for k, v in kt.items():

@@ -8,8 +8,8 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 timeout -k 10 600 python3 -u -m pytest -x -v --timeout 300 --timeout-method thread tests -m gpu > $OUT/tests_gpu.log 2>&1 || exit $?
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || exit $?
-timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_drv.json 2> $OUT/bench_drv.err || exit $?
-timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_drv2.json 2> $OUT/bench_drv2.err || exit $?
+timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_drv.json 2> $OUT/bench_drv.err || exit $?
+timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_drv2.json 2> $OUT/bench_drv2.err || exit $?
 bash tools/trace_driver.sh $TAG || exit $?
 bash tools/pmc_traffic.sh $TAG || exit $?
 # throughput against N (config 3: 2^14..2^25, config 4: 2^18..2^24), then the SQ counters of the

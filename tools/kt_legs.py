@@ -1,8 +1,8 @@
-"""Per-leg step-kernel durations from a rocprofv3 kernel trace of bench.py.
+"""Per-leg step-kernel durations from a rocprofv3 kernel trace of bench.py --full.
 
     python tools/kt_legs.py <kernel_trace.csv> [--bench bench.json] [--steps K] [--warmup W]
 
-bench.py runs its legs in a fixed order, so the step launches of each leg are the
+bench.py --full runs its legs in a fixed order, so the step launches of each leg are the
 next dispatches of that leg's kernel instantiation in the trace:
   config 3   step_kernel<false, false, false, true, false, false> (kNt loads, N = 2^20, se_step):
              the from-reset leg's W + K launches, then the headline leg's P3 pre-roll steps

@@ -12,7 +12,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o kt_drv -- \
-    python3 "$R/bench.py" --gpus 1 --steps 20 --warmup 5 "$@" > "$OUT/kt_drv.log" 2>&1
+    python3 "$R/bench.py" --gpus 1 --steps 20 --warmup 5 --full "$@" > "$OUT/kt_drv.log" 2>&1
 rc=$?
 cd "$R"
 [ $rc -eq 0 ] || { tail -5 "$OUT/kt_drv.log"; exit $rc; }
