@@ -154,20 +154,27 @@ int se_reset_to(se_env* env, const uint8_t* mask, const int32_t* origin, const i
  * (step counter, slot); the step counter advances by one per call. */
 int se_step(se_env* env, const int32_t* actions, void* stream);
 
-/* `steps` consecutive se_step calls issued from native code: step k takes its actions
- * from actions + k * ld (ld >= n int32 entries, 16-byte aligned rows). The same
- * launches as a host loop over se_step, without the caller's per-step overhead, so a
- * fixed action schedule keeps the GPU queue full (a rollout of a pre-computed policy,
- * the bench's timed region). reward/done/err hold the last step's outputs. The kernel
- * is the same code as se_step's, under a name of its own in a kernel trace (without
- * auto-reset). An extension: the reference steps one call at a time
+/* `steps` consecutive steps issued from native code: step k takes its actions from
+ * actions + k * ld (ld >= n int32 entries, 16-byte aligned rows), for a fixed action
+ * schedule (a rollout of a pre-computed policy, the bench's timed region).
+ * Guaranteed: the final state (x, y, fuel, cargo, origin, dest), the last step's reward, done
+ * and err, and the step counter equal `steps` se_step calls on the same rows, bit for bit.
+ * Without auto-reset the run is fused: the state of an env stays in registers from step
+ * to step (step_seq_kernel; one launch per run of at most SHIPENV_SEQ_MAX_STEPS steps,
+ * default 1024, read at se_create), so the intermediate steps' reward, done and err are
+ * NOT written: the buffers hold the last step's alone, as the state buffers hold only
+ * the final state. SHIPENV_SEQ_FUSE=0 at se_create issues one se_step launch per step
+ * instead (the same kernel code as se_step's under a trace name of its own). With
+ * auto-reset the run is always a launch per step (done lists, statistics and episode
+ * counters are per step). An extension: the reference steps one call at a time
  * (environment.py:359-376). */
 int se_step_seq(se_env* env, const int32_t* actions, int64_t ld, int32_t steps, void* stream);
 
 /* se_step_seq that also records `event` (a hipEvent_t, may be NULL) on the stream right
- * after launch number `mark_after` (0..steps; 0 = before the first launch): a timer mark
+ * after step number `mark_after` (0..steps; 0 = before the first launch): a timer mark
  * in the same native call as the launches, with no host round trip between them
- * (tools/diag/wall_forms.py). */
+ * (tools/diag/wall_forms.py). A fused run is split there: steps [0, mark_after), the
+ * event, steps [mark_after, steps). */
 int se_step_seq_mark(se_env* env, const int32_t* actions, int64_t ld, int32_t steps, void* stream,
                      void* event, int32_t mark_after);
 

@@ -1080,6 +1080,16 @@ struct Draws {
     U4 fuel, gate, loss0, arrive;
 };
 template <bool kSpecLoss>
+__device__ __forceinline__ Draws early_draws(const StepArgs& A, int64_t base, uint32_t t) {
+    const Key qk = env_key(A.seed, (A.env_base + base) >> 2);
+    Draws d;
+    d.fuel = draw(qk, t, kSlotFuel);
+    d.gate = draw(qk, t, kSlotGate);
+    d.loss0 = kSpecLoss ? draw(qk, t, loss_slot(0)) : U4{{0u, 0u, 0u, 0u}};
+    d.arrive = U4{{0u, 0u, 0u, 0u}};
+    return d;
+}
+template <bool kSpecLoss>
 __device__ __forceinline__ Draws early_draws(const StepArgs& A, int64_t base) {
     const Key qk = env_key(A.seed, (A.env_base + base) >> 2);
     Draws d;
@@ -1163,18 +1173,33 @@ __device__ __forceinline__ uint32_t record_group(const StepArgs& A, int64_t base
 // fire, lose nothing, and still consume the loss-type draw), the loss type, beta and
 // the arrival's new destination; SE_USED_* bits back in the tape, and a step that needs
 // a variate the tape lacks leaves its env untouched with SE_ERR_NEED_DRAW.
-template <bool kAuto, bool kFull, bool kNt, bool kRec = false, bool kReplay = false>
+//
+// kKeep (step_seq_kernel: a full group, Philox draws, no auto-reset): the step runs at
+// counter tk instead of A.t and stores nothing. The post-step x, y, fuel, cargo, origin and
+// dest go back into G in its packed form, so the next step of a fused sequence reads them
+// from registers, and the step's reward, done bytes and err bytes are returned in *O; the
+// caller stores the state and the last step's outputs once. The arithmetic is the per-step
+// code's, untouched. (tk and O are trailing defaults, not a wrapper: the per-step
+// instantiations then compile to the instructions they had before.)
+struct StepOut {
+    float rw[4];
+    uint32_t dn, ee;  // done / err of the group, packed u8 x4
+};
+template <bool kAuto, bool kFull, bool kNt, bool kRec = false, bool kReplay = false, bool kKeep = false>
 __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWorld& w,
                                                  Group<false, kAuto, kNt>& G, At<kFull> at,
-                                                 BlockStats& bs, Finished& F, const Draws& D) {
+                                                 BlockStats& bs, Finished& F, const Draws& D,
+                                                 [[maybe_unused]] uint32_t tk = 0,
+                                                 [[maybe_unused]] StepOut* O = nullptr) {
     static_assert(!kReplay || (!kAuto && !kRec), "agent replay: no auto-reset, no ring record");
+    static_assert(!kKeep || (kFull && !kAuto && !kRec && !kReplay), "fused sequence: full groups, no auto-reset");
     const int64_t n = A.n, base = at.base;
     const int P = w.P;
     const uint32_t lim = (uint32_t)(w.H - 1) | ((uint32_t)(w.W - 1) << 16);
     const uint32_t wh = (uint32_t)w.W | (1u << 16);
     const uint32_t pm1 = P > 0 ? (uint32_t)(P - 1) : 0u;  // clamp for table reads whose value an error discards
     const Key qk = env_key(A.seed, (A.env_base + base) >> 2);
-    const uint32_t t = A.t;
+    const uint32_t t = kKeep ? tk : A.t;  // the step counter: the sequence's, or the launch's
     constexpr bool kSpecLoss = spec_loss<kAuto>();
 #if SHIPENV_TRACE
     __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the group's data has arrived
@@ -1357,14 +1382,23 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
             }
             record_early(late_args(), base, flags4, nf);
         }
-        const se_state& S = A.st;
-        __builtin_amdgcn_sched_barrier(0);  // the fuel halves back to back (store_moved)
-        store4u8(S.x, at, ox);
-        store4u8(S.y, at, oy);
-        store4(S.fuel, at, f);
-        store4u8(S.done, at, dn);
-        store4u8(reinterpret_cast<uint8_t*>(S.err), at, ee);
-        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (kKeep) {
+            G.x = ox;
+            G.y = oy;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) G.f[j] = f[j];
+            O->dn = dn;
+            O->ee = ee;
+        } else {
+            const se_state& S = A.st;
+            __builtin_amdgcn_sched_barrier(0);  // the fuel halves back to back (store_moved)
+            store4u8(S.x, at, ox);
+            store4u8(S.y, at, oy);
+            store4(S.fuel, at, f);
+            store4u8(S.done, at, dn);
+            store4u8(reinterpret_cast<uint8_t*>(S.err), at, ee);
+            __builtin_amdgcn_sched_barrier(0);
+        }
     }
     TRACE_STAMP(6);
 
@@ -1477,6 +1511,16 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
         od |= (uint32_t)(dst[j] & 0xff) << (8 * j);
     }
     if constexpr (kAuto) F.mask = fin;
+    if constexpr (kKeep) {
+        G.org = oo;
+        G.dst = od;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            G.c[j] = cg[j];
+            O->rw[j] = rw[j];
+        }
+        return;
+    }
     const se_state& S = late_args().st;
     store4u8(S.origin, at, oo);
     store4u8(S.dest, at, od);
@@ -1767,6 +1811,84 @@ template <bool kTyped, bool kReplay, bool kAuto>
 __global__ __launch_bounds__(64) void step_tail_kernel(StepArgs A) {
     if (threadIdx.x != 0) return;
     step_tail_envs<kTyped, kReplay, kAuto>(A, world_view(A.dims, A.world));
+}
+
+// se_step_seq without auto-reset, fused: `steps` consecutive steps of the agent path in one
+// launch, on step_kernel's grid and ownership. Nothing outside the stream can observe the
+// state between two steps of one sequence, and a step reads only x, y, origin, dest, cargo,
+// fuel and its action, so a group is loaded once, stepped `steps` times in registers
+// (step_group_agent<kKeep>: counter A.t + k, action row k at A.act + k * ld) and stored once,
+// with the last step's reward, done and err. Against a launch per step that leaves out, per
+// step, the launch, the world staging, 32 B of state loads and 38 B of stores per env; what a
+// step still moves is its 4 B action. Row k + 1 is loaded before step k's arithmetic, so its
+// latency (rows are read once, from HBM) hides behind the step. iters > 1: the group loop is
+// the outer one.
+template <bool kNt>
+__global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4))) void step_seq_kernel(
+    StepArgs A, int32_t steps, int64_t ld) {
+    extern __shared__ uint32_t lds[];
+    if (steps <= 0) return;  // nothing to store (the host launches no empty run)
+    const int64_t full = A.n >> 2;
+    const int64_t first = (int64_t)blockIdx.x * A.iters * kStepBlock;  // block-uniform first group
+
+    const Staged st = stage_issue(A.world);
+    __builtin_amdgcn_sched_barrier(0);
+    // first group: step_kernel's clamped, unconditional load (state and action row 0)
+    Group<false, false, kNt> G;
+    {
+        const int64_t last = full - 1 - first;  // block-uniform
+        const uint32_t lane = last < (int64_t)threadIdx.x ? (uint32_t)(last < 0 ? 0 : last) : threadIdx.x;
+        G.template load<true>(A, At<true>{last < 0 ? full - 1 : first, 0, A.n}, lane);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const LdsWorld w = stage_finish(A.world, A.dims, lds, st);
+
+    BlockStats bs;
+    Finished F;
+    for (int64_t i = 0; i < A.iters; ++i) {
+        const int64_t g0 = first + i * kStepBlock, g = g0 + threadIdx.x;
+        if (g >= full) break;  // no barrier below
+        if (i > 0) G.template load<true>(A, At<true>{g0, 0, A.n});
+        const At<true> at{g0, g * 4, A.n};
+        StepOut O;
+        for (int32_t k = 0; k < steps; ++k) {
+            // the next row's actions (the last step reads its own row again: no branch)
+            const int32_t kn = k + 1 < steps ? k + 1 : k;
+            int32_t nxt[4];
+            ld4_full<kNt>(A.act + (int64_t)kn * ld, g0, nxt);
+            const uint32_t t = A.t + (uint32_t)k;
+            const Draws D = early_draws<false>(A, g * 4, t);
+            step_group_agent<false, true, kNt, false, false, true>(A, w, G, at, bs, F, D, t, &O);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
+        }
+        const se_state& S = late_args().st;
+        __builtin_amdgcn_sched_barrier(0);  // the fuel halves back to back (store_moved)
+        st4u8_full(S.x, g0, G.x);
+        st4u8_full(S.y, g0, G.y);
+        st4_full(S.fuel, g0, G.f);
+        st4u8_full(S.done, g0, O.dn);
+        st4u8_full(reinterpret_cast<uint8_t*>(S.err), g0, O.ee);
+        __builtin_amdgcn_sched_barrier(0);
+        st4u8_full(S.origin, g0, G.org);
+        st4u8_full(S.dest, g0, G.dst);
+        st4_full(S.cargo, g0, G.c);
+        st4_full(S.reward, g0, O.rw);
+    }
+}
+
+// The partial last group of a fused sequence: one thread steps its at most 3 envs `steps`
+// times with step_tail_envs, loading and storing per step.
+__global__ __launch_bounds__(64) void step_tail_seq_kernel(StepArgs A, int32_t steps, int64_t ld) {
+    if (threadIdx.x != 0) return;
+    const LdsWorld w = world_view(A.dims, A.world);
+    const int32_t* act = A.act;
+    const uint32_t t0 = A.t;
+    for (int32_t k = 0; k < steps; ++k) {
+        A.act = act + (int64_t)k * ld;
+        A.t = t0 + (uint32_t)k;
+        step_tail_envs<false, false, false>(A, w);
+    }
 }
 
 // Contiguous copy of the last step's done lists (se_done_compact), in two launches:
@@ -2436,6 +2558,8 @@ struct se_env {
     bool mask_tiled = false;         // SHIPENV_MASK_TILED=1 at se_create: the round-4 tiled kernel
     int32_t done_pad = 1;   // done-list records padded to runs of this many (done_pad_records)
     bool nt_loads = false;  // nontemporal state loads in the step kernel (step_nt_loads)
+    bool seq_fuse = true;   // se_step_seq without auto-reset: one launch per run (SHIPENV_SEQ_FUSE=0: one per step)
+    int32_t seq_max_steps = 1024;  // steps of one fused launch at most (seq_max_steps)
 };
 
 // A host-resident world (se_host_*): no device, no HIP call. It steps envs whose SoA
@@ -2526,6 +2650,22 @@ bool step_nt_loads(const se_env* env) {
     if (v) return atoi(v) != 0;
     if (env->flags & SE_FLAG_AUTO_RESET) return env->n > (int64_t)1 << 21;
     return env->n <= (int64_t)1 << 23;
+}
+
+// se_step_seq's fused launches (step_seq_kernel) hold the queue for their whole run: about
+// 3.5 ms for 1024 steps at 2^20 envs. A longer sequence goes out as several launches of at
+// most this many steps. SHIPENV_SEQ_MAX_STEPS overrides; SHIPENV_SEQ_FUSE=0 issues one
+// step_kernel<..., kSeq> launch per step instead (the A/B baseline). Both are resolved
+// once, by se_create.
+constexpr int32_t kSeqMaxSteps = 1024;
+int32_t seq_max_steps() {
+    const char* v = getenv("SHIPENV_SEQ_MAX_STEPS");
+    const int c = v ? atoi(v) : 0;
+    return c > 0 ? c : kSeqMaxSteps;
+}
+bool seq_fuse() {
+    const char* v = getenv("SHIPENV_SEQ_FUSE");
+    return !v || atoi(v) != 0;
 }
 
 size_t lds_bytes(const se_env* env) { return (size_t)env->dims.padded() * 4; }
@@ -2693,6 +2833,36 @@ int launch_step(se_env* env, bool typed, bool replay, const int32_t* act, const 
     return SE_OK;
 }
 
+// `steps` > 0 consecutive agent steps without auto-reset as one fused launch (plus the
+// partial last group's), rows `ld` apart from act; the caller checked the env and the stride.
+int launch_step_seq(se_env* env, const int32_t* act, int64_t ld, int32_t steps, void* stream) {
+    if (!act) return fail(SE_EINVAL, "null action/tape pointer");
+    if (!aligned16(act)) return fail(SE_EINVAL, "action buffers must be 16-byte aligned");
+    DeviceGuard g(env->device);
+    StepArgs A{};
+    A.world = env->d_world;
+    A.dims = env->dims;
+    A.n = env->n;
+    A.env_base = env->env_base;
+    A.seed = env->seed;
+    A.t = (uint32_t)env->step_t;
+    A.st = env->st;
+    A.act = act;
+    A.iters = env->iters;
+    const hipStream_t s = (hipStream_t)stream;
+    if (env->n >= kEnvsPerThread) {  // at least one full group (the kernel's first load assumes it)
+        if (env->nt_loads) step_seq_kernel<true><<<env->grid, kStepBlock, lds_bytes(env), s>>>(A, steps, ld);
+        else step_seq_kernel<false><<<env->grid, kStepBlock, lds_bytes(env), s>>>(A, steps, ld);
+        HIP_TRY(hipGetLastError());
+    }
+    if (env->n & 3) {
+        step_tail_seq_kernel<<<1, 64, 0, s>>>(A, steps, ld);
+        HIP_TRY(hipGetLastError());
+    }
+    env->step_t += (uint64_t)steps;
+    return SE_OK;
+}
+
 }  // namespace
 
 // error text for se_last_error from the host-only sources (mapload.cpp)
@@ -2753,6 +2923,8 @@ int se_create(se_env** out, int device, int64_t n, int64_t env_id_base, int32_t 
         env->nslab = (int64_t)env->grid * (kStepBlock / 64);  // stats: one entry per wave
         env->done_pad = done_pad_records(env);
         env->nt_loads = step_nt_loads(env);
+        env->seq_fuse = seq_fuse();
+        env->seq_max_steps = seq_max_steps();
         const char* mv = getenv("SHIPENV_MASK_TILED");
         env->mask_tiled = mv && atoi(mv) != 0;
     }
@@ -2838,13 +3010,25 @@ int se_step_seq_mark(se_env* env, const int32_t* actions, int64_t ld, int32_t st
     if (steps < 0) return fail(SE_EINVAL, "negative step count");
     if (steps > 1 && (ld < env->n || (ld & 3))) return fail(SE_EINVAL, "row stride must be >= n and a multiple of 4");
     if (event && (mark_after < 0 || mark_after > steps)) return fail(SE_EINVAL, "mark_after must be in [0, steps]");
-    for (int32_t k = 0; k <= steps; ++k) {
+    // without auto-reset nothing reads the state between two steps of the run: fused launches
+    // (step_seq_kernel), split where the event goes and at seq_max_steps. Auto-reset keeps a
+    // launch per step (its done lists and statistics are per step).
+    const bool fused = env->seq_fuse && env->n > 0 && !(env->flags & SE_FLAG_AUTO_RESET);
+    for (int32_t k = 0; k <= steps;) {
         if (event && k == mark_after) {
             DeviceGuard g(env->device);
             HIP_TRY(hipEventRecord((hipEvent_t)event, (hipStream_t)stream));
         }
         if (k == steps) break;
-        rc = launch_step(env, false, false, actions + (int64_t)k * ld, nullptr, nullptr, nullptr, stream, nullptr, true);
+        if (fused) {
+            const int32_t end = event && k < mark_after ? mark_after : steps;
+            const int32_t run = std::min(end - k, env->seq_max_steps);
+            rc = launch_step_seq(env, actions + (int64_t)k * ld, ld, run, stream);
+            k += run;
+        } else {
+            rc = launch_step(env, false, false, actions + (int64_t)k * ld, nullptr, nullptr, nullptr, stream, nullptr, true);
+            k += 1;
+        }
         if (rc) return rc;
     }
     return SE_OK;

@@ -210,12 +210,17 @@ class VecEnv:
         return self.reward, self.done, self.err
 
     def step_seq(self, actions, mark=None, mark_after=0):
-        """len(actions) consecutive step() calls issued from native code (se_step_seq):
-        actions is an int32 device tensor [K, n] (rows contiguous, 16-byte aligned), row k
-        the actions of step k. mark: a torch.cuda.Event recorded on the current stream right
-        after launch `mark_after` (se_step_seq_mark; 0 = before launch 1, the timed loop's
-        form; at most K), a timer mark inside the one native call. Returns the last
-        step's (reward, done, err)."""
+        """len(actions) consecutive steps issued from native code (se_step_seq): actions is
+        an int32 device tensor [K, n] (rows contiguous, 16-byte aligned), row k the actions of
+        step k. The state it leaves, the step counter and the returned last step's (reward,
+        done, err) equal K step() calls on the same rows bit for bit. Without auto-reset the K
+        steps run fused, the state in registers from step to step (one launch per run of at
+        most SHIPENV_SEQ_MAX_STEPS steps, default 1024), so the intermediate steps' reward,
+        done and err are never written; SHIPENV_SEQ_FUSE=0 when the env is made selects a
+        launch per step. With auto-reset it is always a launch per step. mark: a
+        torch.cuda.Event recorded on the current stream right after step `mark_after`
+        (se_step_seq_mark; 0 = before the first launch, the timed loop's form; at most K), a
+        timer mark inside the one native call; a fused run is split there."""
         a = actions
         if not (type(a) is torch.Tensor and a.dtype is torch.int32 and a.is_cuda and a.dim() == 2
                 and a.get_device() == self._dev_index and a.shape[1] == self.n and a.stride(1) == 1
