@@ -317,7 +317,10 @@ int se_qnet_create(se_qnet** out, se_env* env);
 /* Weights: DEVICE f32 arrays in torch nn.Linear layout (weight [out][in], bias [out]):
  * w1 [128][6+4P], b1 [128], w2 [128][128], b2 [128], w3 [A][128], b3 [A]. Packed on the
  * stream (bf16, MFMA fragment order). Call again after se_set_ports (the port block is
- * folded with the ports of that moment; se_policy refuses a stale packing). */
+ * folded with the ports of that moment; se_policy refuses a stale packing).
+ * Worlds of 1..64 ports: the policy keeps each env's valid SELECT rows as one 64-bit
+ * word, so more ports return SE_EINVAL ("the fused policy supports 1..64 ports"); the
+ * env itself stays usable (se_qtrain_create has the same limit). */
 int se_qnet_set_weights(se_qnet* q, const float* w1, const float* b1, const float* w2,
                         const float* b2, const float* w3, const float* b3, void* stream);
 /* actions[i]: the agent-index action (se_step input) for every env. Exploration draws

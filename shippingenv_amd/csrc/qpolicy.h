@@ -1634,7 +1634,8 @@ int se_qnet_set_weights(se_qnet* qn, const float* w1, const float* b1, const flo
     if (!qn) return fail(SE_EINVAL, "null qnet");
     if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3) return fail(SE_EINVAL, "null weight pointer");
     se_env* env = qn->env;
-    if (env->dims.P < 1) return fail(SE_EINVAL, "the policy needs at least one port");
+    // SELECT validity is one uint64_t per port (SAME, sel): bit p is port p, so 64 ports at most
+    if (env->dims.P < 1 || env->dims.P > 64) return fail(SE_EINVAL, "the fused policy supports 1..64 ports");
     DeviceGuard g(env->device);
     const QnetDims q = qnet_dims(env->dims.P);
     const QnetDims qc = qnet_dims(env->dims.P, true, env->cmax, env->fmax);
