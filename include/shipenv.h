@@ -163,7 +163,9 @@ int se_step(se_env* env, const int32_t* actions, void* stream);
  * to step (step_seq_kernel; one launch per run of at most SHIPENV_SEQ_MAX_STEPS steps,
  * default 1024, read at se_create), so the intermediate steps' reward, done and err are
  * NOT written: the buffers hold the last step's alone, as the state buffers hold only
- * the final state. SHIPENV_SEQ_FUSE=0 at se_create issues one se_step launch per step
+ * the final state. The steps of a launch before its last do not compute reward, done or
+ * err at all, only the state (the last step of every launch is a full one).
+ * SHIPENV_SEQ_FUSE=0 at se_create issues one se_step launch per step
  * instead (the same kernel code as se_step's under a trace name of its own). With
  * auto-reset the run is always a launch per step (done lists, statistics and episode
  * counters are per step). An extension: the reference steps one call at a time

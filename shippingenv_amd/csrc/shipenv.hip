@@ -1181,18 +1181,36 @@ __device__ __forceinline__ uint32_t record_group(const StepArgs& A, int64_t base
 // caller stores the state and the last step's outputs once. The arithmetic is the per-step
 // code's, untouched. (tk and O are trailing defaults, not a wrapper: the per-step
 // instantiations then compile to the instructions they had before.)
+//
+// kLean (with kKeep only: the steps of a fused sequence before its last): the state-only
+// step. Nothing can read an inner step's reward, done or err, and without auto-reset the next
+// state needs neither the out-of-fuel flag (a dead ship keeps moving) nor which error was
+// raised, only whether one was. So the mode computes no reward (no closer test, no reward
+// table read, no f64 loss / arrival adds, no f32 conversion), no out-of-fuel compare, and the
+// action's checks as one bit instead of the error code; *O is not touched. Position, origin
+// and dest are read from and written to *U, one register per env, instead of G's packed
+// bytes, so consecutive lean steps neither unpack nor pack them; fuel, cargo and the action
+// stay in G. The state arithmetic, its order, the LDS lookups that feed it and every Philox
+// counter are the full step's.
 struct StepOut {
     float rw[4];
     uint32_t dn, ee;  // done / err of the group, packed u8 x4
 };
-template <bool kAuto, bool kFull, bool kNt, bool kRec = false, bool kReplay = false, bool kKeep = false>
+struct Carried {
+    uint32_t pos[4];  // x | y << 16
+    int org[4], dst[4];
+};
+template <bool kAuto, bool kFull, bool kNt, bool kRec = false, bool kReplay = false, bool kKeep = false,
+          bool kLean = false>
 __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWorld& w,
                                                  Group<false, kAuto, kNt>& G, At<kFull> at,
                                                  BlockStats& bs, Finished& F, const Draws& D,
                                                  [[maybe_unused]] uint32_t tk = 0,
-                                                 [[maybe_unused]] StepOut* O = nullptr) {
+                                                 [[maybe_unused]] StepOut* O = nullptr,
+                                                 [[maybe_unused]] Carried* U = nullptr) {
     static_assert(!kReplay || (!kAuto && !kRec), "agent replay: no auto-reset, no ring record");
     static_assert(!kKeep || (kFull && !kAuto && !kRec && !kReplay), "fused sequence: full groups, no auto-reset");
+    static_assert(!kLean || kKeep, "state-only step: only inside a fused sequence (kKeep), whose last step is a full one");
     const int64_t n = A.n, base = at.base;
     const int P = w.P;
     const uint32_t lim = (uint32_t)(w.H - 1) | ((uint32_t)(w.W - 1) << 16);
@@ -1207,7 +1225,8 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
 #endif
     // --- first half: everything that needs no optional draw (:359-376, :273-315)
     uint32_t pos[4], pd16[4];
-    int val[4], dst[4], cg[4], err[4], ridx[4];
+    int val[4], dst[4], cg[4];
+    [[maybe_unused]] int err[4], ridx[4];  // not in the state-only step
     bool do_move[4], moved[4], tf_ok[4];
     bool gate_needed = false;
 #pragma unroll
@@ -1219,8 +1238,14 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
         val[j] = act - 4 - (lt_sel ? 0 : P) - (lt_tc ? 0 : 50);
         const uint32_t dxy = w.moves[act & 3];
         // packed position x | y << 16 from the group's x and y bytes
-        const uint32_t p = __builtin_amdgcn_perm(G.y, G.x, (uint32_t)j | 0x0c000c00u | ((uint32_t)(4 + j) << 16));
-        dst[j] = byte_of(G.dst, j);
+        uint32_t p;
+        if constexpr (kLean) {
+            p = U->pos[j];
+            dst[j] = U->dst[j];
+        } else {
+            p = __builtin_amdgcn_perm(G.y, G.x, (uint32_t)j | 0x0c000c00u | ((uint32_t)(4 + j) << 16));
+            dst[j] = byte_of(G.dst, j);
+        }
         cg[j] = G.c[j];
         // MOVE (_move_ship :273-339)
         const uint32_t np = pk_add_u16(p, dxy);
@@ -1229,23 +1254,34 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
         const uint32_t cp = (!nodest & inb) ? np : p;  // in-range cell for the lookups
         const bool ground = w.cell[cell_of(cp, wh)] == kCellGround;  // :293
         pd16[j] = w.pos[min((uint32_t)dst[j], pm1)];
-        const bool closer = dist2(p, pd16[j]) > dist2(cp, pd16[j]);  // old vs ATTEMPTED cell (:307-315)
+        [[maybe_unused]] bool closer = false;  // old vs ATTEMPTED cell (:307-315)
+        if constexpr (!kLean) closer = dist2(p, pd16[j]) > dist2(cp, pd16[j]);
         // TAKE_* (:341-357) at the port on the ship's cell; SELECT_PORT (:265-271)
         const int k = (int)w.cell[cell_of(p, wh)] - 1;
         const bool atport = (uint32_t)k < (uint32_t)P;
         const int2 st2 = w.stock[min((uint32_t)k, pm1)];
         const int stock = lt_tc ? st2.y : st2.x;
         const bool amount_bad = (val[j] <= 0) | (val[j] > stock);
-        const bool same = byte_of(G.org, j) == val[j];
-        const int e_move = nodest ? SE_ERR_NO_DEST : (inb ? SE_ERR_OK : SE_ERR_OOB);
-        const int e_sel = same ? SE_ERR_SAME_PORT : SE_ERR_OK;
-        const int e_amt = amount_bad ? SE_ERR_AMOUNT : SE_ERR_OK;
-        const int e_take = atport ? e_amt : SE_ERR_NOT_AT_PORT;
-        const int e_ns = lt_sel ? e_sel : e_take;
-        const int e_ty = is_mv ? e_move : e_ns;
-        const int e_p = P == 0 ? SE_ERR_NO_PORTS : e_ty;  // :360
-        err[j] = bad ? SE_ERR_BAD_INDEX : e_p;            // the decode runs before env.step
-        const bool ok = err[j] == SE_ERR_OK;
+        const bool same = (kLean ? U->org[j] : byte_of(G.org, j)) == val[j];
+        bool ok;
+        if constexpr (kLean) {
+            // the cascade below as its one bit: no check of the action's own type failed
+            // (mask arithmetic, no ?: : a branch here would take the LDS lookups with it)
+            const bool ok_mv = is_mv & !nodest & inb;
+            const bool ok_sel = !is_mv & lt_sel & !same;
+            const bool ok_take = !lt_sel & atport & !amount_bad;
+            ok = !bad & (P != 0) & (ok_mv | ok_sel | ok_take);
+        } else {
+            const int e_move = nodest ? SE_ERR_NO_DEST : (inb ? SE_ERR_OK : SE_ERR_OOB);
+            const int e_sel = same ? SE_ERR_SAME_PORT : SE_ERR_OK;
+            const int e_amt = amount_bad ? SE_ERR_AMOUNT : SE_ERR_OK;
+            const int e_take = atport ? e_amt : SE_ERR_NOT_AT_PORT;
+            const int e_ns = lt_sel ? e_sel : e_take;
+            const int e_ty = is_mv ? e_move : e_ns;
+            const int e_p = P == 0 ? SE_ERR_NO_PORTS : e_ty;  // :360
+            err[j] = bad ? SE_ERR_BAD_INDEX : e_p;            // the decode runs before env.step
+            ok = err[j] == SE_ERR_OK;
+        }
         do_move[j] = ok & is_mv;
         moved[j] = do_move[j] & !ground;
         const bool take_ok = ok & !lt_sel;
@@ -1257,8 +1293,10 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
         dst[j] = sel_ok ? val[j] : dst[j];
         // reward row before loss / arrival: a move by (out_of_fuel, ground, closer),
         // filled in once fuel is known; a take 0.05; anything else 0
-        const int r_rest = take_ok ? 8 : 9;
-        ridx[j] = do_move[j] ? (((int)ground << 1) | (int)closer) : r_rest;
+        if constexpr (!kLean) {
+            const int r_rest = take_ok ? 8 : 9;
+            ridx[j] = do_move[j] ? (((int)ground << 1) | (int)closer) : r_rest;
+        }
         gate_needed |= !bad & is_mv & !nodest & inb & (G.c[j] > 0) & (G.c[j] < 50);
     }
     TRACE_STAMP(5);
@@ -1266,7 +1304,8 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
     const U4 fb = D.fuel;
     const U4 gb = D.gate;
     uint32_t fire = 0, arrive = 0, fin = 0, dead = 0;
-    double f[4], r[4];
+    double f[4];
+    [[maybe_unused]] double r[4];  // not in the state-only step
     // kReplay: the group's tape records (the partial last group's missing envs read none)
     [[maybe_unused]] double tu[4], tg[4], tt[4], tb[4];
     [[maybe_unused]] int td[4];
@@ -1289,7 +1328,8 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
         double scale;
         if constexpr (kReplay) scale = 1.0 + (-0.1 + 0.2 * tu[j]);
         else scale = 1.0 + (-0.1 + (double)fb.v[j] * kFifthPerWord);
-        const bool oof = G.f[j] < scale;  // :288-290 (the ship still moves)
+        [[maybe_unused]] bool oof = false;  // :288-290 (the ship still moves)
+        if constexpr (!kLean) oof = G.f[j] < scale;
         const double take = tf_ok[j] ? (double)val[j] : -0.0;
         f[j] = G.f[j] + (moved[j] ? -scale : take);
         // the gate random() <= cargo / 50 (:318-323) as w <= floor(fl(c/50) 2^32); the
@@ -1304,18 +1344,21 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
             const uint32_t thr = w.gate_thr[min(max(cg[j], 0), 50)];
             fires = do_move[j] & (cg[j] > 0) & (gb.v[j] <= thr);
         }
-        r[j] = w.rtab[ridx[j] | ((int)(do_move[j] & oof) << 2)];
+        if constexpr (!kLean) r[j] = w.rtab[ridx[j] | ((int)(do_move[j] & oof) << 2)];
         fire |= (uint32_t)fires << j;
         arrive |= (uint32_t)(do_move[j] & (pos[j] == pd16[j])) << j;  // :325
-        dead |= (uint32_t)(do_move[j] & oof) << j;
-        fin |= (uint32_t)((kFull || base + j < n) & do_move[j] & oof) << j;
+        if constexpr (!kLean) {
+            dead |= (uint32_t)(do_move[j] & oof) << j;
+            fin |= (uint32_t)((kFull || base + j < n) & do_move[j] & oof) << j;
+        }
     }
     // the flags travel as opaque VGPR bit masks (no lane masks live in SGPR pairs
-    // across the draw blocks below)
-    asm volatile("" : "+v"(fire), "+v"(arrive), "+v"(fin), "+v"(dead));
+    // across the draw blocks below); the state-only step has no dead / fin to keep
+    if constexpr (kLean) asm volatile("" : "+v"(fire), "+v"(arrive));
+    else asm volatile("" : "+v"(fire), "+v"(arrive), "+v"(fin), "+v"(dead));
     int org[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) org[j] = byte_of(G.org, j);
+    for (int j = 0; j < 4; ++j) org[j] = kLean ? U->org[j] : byte_of(G.org, j);
 
     // auto-reset (:227-243) of the envs that ran out of fuel: position and fuel now,
     // cargo / origin / dest after the second half (whose reward the finished episode
@@ -1357,7 +1400,13 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
     }
     // x, y, fuel, done and err are final here (cargo loss and arrival change none)
     uint32_t rec_x = 0, rec_y = 0, rec_cut = 0;
-    {
+    if constexpr (kLean) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            U->pos[j] = pos[j];
+            G.f[j] = f[j];
+        }
+    } else {
         const uint32_t t01 = __builtin_amdgcn_perm(pos[1], pos[0], 0x06020400u);  // x0 x1 y0 y1
         const uint32_t t23 = __builtin_amdgcn_perm(pos[3], pos[2], 0x06020400u);  // x2 x3 y2 y3
         const uint32_t ox = __builtin_amdgcn_perm(t23, t01, 0x05040100u);
@@ -1458,8 +1507,10 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
             const int some = lt[j] > kTypeHi ? cg[j] : part;
             const int loss = lt[j] < kTypeLo ? 0 : some;
             const bool fj = (fire >> j) & 1u;
-            const double rl = r[j] + (double)loss * -3.0;  // int(loss * -3) exactly, then += (:323)
-            r[j] = fj ? rl : r[j];
+            if constexpr (!kLean) {
+                const double rl = r[j] + (double)loss * -3.0;  // int(loss * -3) exactly, then += (:323)
+                r[j] = fj ? rl : r[j];
+            }
             cg[j] = fj ? cg[j] - loss : cg[j];
         }
     }
@@ -1470,7 +1521,8 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const bool aj = (arrive >> j) & 1u;
-            const double ra = (r[j] + (double)(2 * cg[j])) + 10.0;
+            [[maybe_unused]] double ra = 0.0;
+            if constexpr (!kLean) ra = (r[j] + (double)(2 * cg[j])) + 10.0;
             int nd;
             if constexpr (kReplay) {
                 nd = td[j];
@@ -1478,11 +1530,20 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
             } else {
                 nd = pick_other(ab.v[j], P, dst[j]);
             }
-            r[j] = aj ? ra : r[j];
+            if constexpr (!kLean) r[j] = aj ? ra : r[j];
             cg[j] = aj ? 0 : cg[j];
             org[j] = aj ? dst[j] : org[j];
             dst[j] = aj ? nd : dst[j];
         }
+    }
+    if constexpr (kLean) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            U->org[j] = org[j];
+            U->dst[j] = dst[j];
+            G.c[j] = cg[j];
+        }
+        return;
     }
     float rw[4], epr[4];
     int32_t epl[4];  // kRec: the running length after this step (0 for a finished episode)
@@ -1823,6 +1884,10 @@ __global__ __launch_bounds__(64) void step_tail_kernel(StepArgs A) {
 // step still moves is its 4 B action. Row k + 1 is loaded before step k's arithmetic, so its
 // latency (rows are read once, from HBM) hides behind the step. iters > 1: the group loop is
 // the outer one.
+// Only the last step's reward, done and err exist anywhere, so steps 0 .. steps - 2 run the
+// state-only step (step_group_agent<kLean>), with x | y, origin and dest unpacked once before
+// them and packed once after, and step steps - 1 alone runs the full one. Every launch of a
+// split run therefore ends with a full step; steps == 1 is the full step by itself.
 template <bool kNt>
 __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4))) void step_seq_kernel(
     StepArgs A, int32_t steps, int64_t ld) {
@@ -1850,18 +1915,42 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
         if (g >= full) break;  // no barrier below
         if (i > 0) G.template load<true>(A, At<true>{g0, 0, A.n});
         const At<true> at{g0, g * 4, A.n};
-        StepOut O;
-        for (int32_t k = 0; k < steps; ++k) {
-            // the next row's actions (the last step reads its own row again: no branch)
-            const int32_t kn = k + 1 < steps ? k + 1 : k;
-            int32_t nxt[4];
-            ld4_full<kNt>(A.act + (int64_t)kn * ld, g0, nxt);
-            const uint32_t t = A.t + (uint32_t)k;
-            const Draws D = early_draws<false>(A, g * 4, t);
-            step_group_agent<false, true, kNt, false, false, true>(A, w, G, at, bs, F, D, t, &O);
+        const uint32_t tl = A.t + (uint32_t)(steps - 1);  // the last step's counter
+        if (steps > 1) {
+            // steps 0 .. steps - 2, state only: x | y, origin and dest one register per env
+            Carried U;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
+            for (int j = 0; j < 4; ++j) {
+                U.pos[j] = __builtin_amdgcn_perm(G.y, G.x, (uint32_t)j | 0x0c000c00u | ((uint32_t)(4 + j) << 16));
+                U.org[j] = byte_of(G.org, j);
+                U.dst[j] = byte_of(G.dst, j);
+            }
+            const int32_t* row = A.act;
+            for (uint32_t t = A.t; t != tl; ++t) {
+                // the next row's actions (there is one: the last step follows)
+                row += ld;
+                int32_t nxt[4];
+                ld4_full<kNt>(row, g0, nxt);
+                const Draws D = early_draws<false>(A, g * 4, t);
+                step_group_agent<false, true, kNt, false, false, true, true>(A, w, G, at, bs, F, D, t, nullptr, &U);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
+            }
+            // back into the Group's packed bytes (step_group_agent's own packing)
+            const uint32_t t01 = __builtin_amdgcn_perm(U.pos[1], U.pos[0], 0x06020400u);  // x0 x1 y0 y1
+            const uint32_t t23 = __builtin_amdgcn_perm(U.pos[3], U.pos[2], 0x06020400u);  // x2 x3 y2 y3
+            G.x = __builtin_amdgcn_perm(t23, t01, 0x05040100u);
+            G.y = __builtin_amdgcn_perm(t23, t01, 0x07060302u);
+            G.org = G.dst = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                G.org |= (uint32_t)(U.org[j] & 0xff) << (8 * j);
+                G.dst |= (uint32_t)(U.dst[j] & 0xff) << (8 * j);
+            }
         }
+        // the last step in full: its reward, done and err are the run's
+        StepOut O;
+        step_group_agent<false, true, kNt, false, false, true>(A, w, G, at, bs, F, early_draws<false>(A, g * 4, tl), tl, &O);
         const se_state& S = late_args().st;
         __builtin_amdgcn_sched_barrier(0);  // the fuel halves back to back (store_moved)
         st4u8_full(S.x, g0, G.x);
