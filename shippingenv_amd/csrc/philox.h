@@ -53,21 +53,32 @@ struct U4 {
     uint32_t v[4];
 };
 
+// three-way xor in one v_bitop3_b32 (truth table 0x96, gfx950)
+__host__ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+    return a ^ b ^ c;
+#endif
+}
+
 // One 32x32 -> 64-bit product per multiplier (v_mad_u64_u32) instead of a
 // separate mul_hi / mul_lo pair; the key schedule is wave-uniform (scalar).
-__device__ __forceinline__ U4 philox10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+// Compiled for the host too (tools/philox_pair_check.cpp checks draw2 against it there).
+__host__ __device__ __forceinline__ U4 philox10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                        uint32_t k0, uint32_t k1) {
     // The key is opaque here, so each block recomputes its 18 scalar key adds
     // instead of the compiler hoisting every block's schedule out of the step
     // loop: ~20 live SGPRs per block spilled to VGPR lanes (v_readlane + s_nop).
+#ifdef __HIP_DEVICE_COMPILE__
     asm volatile("" : "+s"(k0), "+s"(k1));
+#endif
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
         const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        // three-way xor in one v_bitop3_b32 (truth table 0x96, gfx950)
-        const uint32_t n0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1, k0, 0x96);
-        const uint32_t n2 = __builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), c3, k1, 0x96);
+        const uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, k0);
+        const uint32_t n2 = xor3((uint32_t)(p0 >> 32), c3, k1);
         c1 = (uint32_t)p1;
         c3 = (uint32_t)p0;
         c0 = n0;
@@ -84,8 +95,97 @@ struct Key {
     uint32_t e0, e1;  // global env id
 };
 
-__device__ __forceinline__ U4 draw(const Key& k, uint32_t t, uint32_t slot) {
+__host__ __device__ __forceinline__ U4 draw(const Key& k, uint32_t t, uint32_t slot) {
     return philox10(k.e0, k.e1, t, slot, k.k0, k.k1);
+}
+
+// The FUEL and GATE blocks of one quad at one counter, drawn together (the state-only step of
+// a fused sequence draws both every step). Their counters (e0, e1, t, slot) differ in the slot
+// alone, and the slot enters a block through c3 only, so of rounds 1-3:
+//   round 1  n0 = hi(M1 t) ^ e1 ^ k0 and c1 = lo(M1 t) are common to both blocks;
+//            n2 = hi(M0 e0) ^ slot ^ k1 and c3 = lo(M0 e0) depend on neither t nor state;
+//   round 2  the product M0 n0 and n2' = hi(M0 n0) ^ c3 ^ (k1 + W1) are common; the product
+//            M1 n2 is per slot and step-invariant, so n0' = hi(M1 n2) ^ c1 ^ (k0 + W0) is one
+//            xor per block;
+//   round 3  the product M1 n2' is common; M0 n0' is the first per-block product of a step.
+// PairInv holds the step-invariant parts, computed once per lane before the step loop (n2 itself
+// is read by its product alone, so only the product's halves are kept); draw2
+// computes the common parts once and runs rounds 4-10 as philox10 does. The words are those of
+// draw(k, t, kSlotFuel) and draw(k, t, kSlotGate) bit for bit, for any e1, key and t.
+constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;
+constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
+
+struct PairInv {
+    uint32_t c3;          // lo(M0 e0): round 1's c3 of both blocks
+    uint32_t hi[2], lo[2];  // the halves of M1 n2, n2 = hi(M0 e0) ^ slot ^ k1; [0] FUEL, [1] GATE
+};
+struct U4x2 {
+    U4 fuel, gate;
+};
+
+__host__ __device__ __forceinline__ PairInv pair_invariants(const Key& k) {
+    const uint64_t p0 = (uint64_t)kPhiloxM0 * k.e0;
+    const uint32_t slot[2] = {kSlotFuel, kSlotGate};
+    PairInv v;
+    v.c3 = (uint32_t)p0;
+    for (int b = 0; b < 2; ++b) {
+        const uint64_t p1 = (uint64_t)kPhiloxM1 * xor3((uint32_t)(p0 >> 32), slot[b], k.k1);
+        v.hi[b] = (uint32_t)(p1 >> 32);
+        v.lo[b] = (uint32_t)p1;
+    }
+    return v;
+}
+
+__host__ __device__ __forceinline__ U4x2 draw2(const Key& k, const PairInv& v, uint32_t t) {
+    uint32_t k0 = k.k0, k1 = k.k1;
+    // round 1, common
+    const uint64_t q1 = (uint64_t)kPhiloxM1 * t;
+    const uint32_t n0 = xor3((uint32_t)(q1 >> 32), k.e1, k0);
+    k0 += kPhiloxW0;
+    k1 += kPhiloxW1;
+    // round 2: the common product and n2', one xor per block
+    const uint64_t q0 = (uint64_t)kPhiloxM0 * n0;
+    const uint32_t n2 = xor3((uint32_t)(q0 >> 32), v.c3, k1);
+    const uint32_t c3 = (uint32_t)q0;
+    k1 += kPhiloxW1;
+    // round 3's common product
+    const uint64_t q2 = (uint64_t)kPhiloxM1 * n2;
+    U4 o[2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        // the key opaque per block, as in philox10: each block computes its scalar key adds
+        // where it runs (the compiler moves the two blocks apart) instead of one schedule
+        // held in ~16 SGPRs across the whole step
+        uint32_t r0 = k0, r1 = k1;
+#ifdef __HIP_DEVICE_COMPILE__
+        asm volatile("" : "+s"(r0), "+s"(r1));
+#endif
+        uint32_t a0 = xor3(v.hi[b], (uint32_t)q1, r0);  // round 2's n0
+        uint32_t a1, a2, a3;
+        r0 += kPhiloxW0;
+        {   // round 3
+            const uint64_t p0 = (uint64_t)kPhiloxM0 * a0;
+            a0 = xor3((uint32_t)(q2 >> 32), v.lo[b], r0);
+            a2 = xor3((uint32_t)(p0 >> 32), c3, r1);
+            a1 = (uint32_t)q2;
+            a3 = (uint32_t)p0;
+            r0 += kPhiloxW0;
+            r1 += kPhiloxW1;
+        }
+#pragma unroll
+        for (int r = 3; r < 10; ++r) {
+            const uint64_t p0 = (uint64_t)kPhiloxM0 * a0;
+            const uint64_t p1 = (uint64_t)kPhiloxM1 * a2;
+            a0 = xor3((uint32_t)(p1 >> 32), a1, r0);
+            a2 = xor3((uint32_t)(p0 >> 32), a3, r1);
+            a1 = (uint32_t)p1;
+            a3 = (uint32_t)p0;
+            r0 += kPhiloxW0;
+            r1 += kPhiloxW1;
+        }
+        o[b] = U4{{a0, a1, a2, a3}};
+    }
+    return U4x2{o[0], o[1]};
 }
 
 // integer uniform on [0, m): high word of r * m (bias < m / 2^32)

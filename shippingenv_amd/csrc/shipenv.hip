@@ -1069,6 +1069,27 @@ __device__ __forceinline__ uint32_t cell_of(uint32_t p, uint32_t wh) {
     return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, p), __builtin_bit_cast(u16x2, wh), 0u, false);
 }
 
+// A lane predicate with its complement, for the state-only step: the compare is made once and
+// the complement is an s_not of its lane mask (written `!c`, the compiler folds the negation
+// into a second, inverted v_cmp). Inactive lanes read either way; both bits are per-lane values.
+struct Pred2 {
+    bool t, f;
+};
+__device__ __forceinline__ Pred2 with_complement(bool c) {
+    uint64_t m = __builtin_amdgcn_ballot_w64(c);
+    asm("" : "+s"(m));
+    return Pred2{__builtin_amdgcn_inverse_ballot_w64(m), __builtin_amdgcn_inverse_ballot_w64(~m)};
+}
+// The byte at index x * W + y of an LDS table, the table's LDS address riding in the dot
+// product's accumulator (cell_of, then the pointer add, is one more v_add_u32 of a base that is
+// zero). cell0: lds_address(table).
+typedef __attribute__((address_space(3))) const uint8_t lds_u8;
+__device__ __forceinline__ uint32_t lds_address(const uint8_t* p) { return (uint32_t)(uintptr_t)(lds_u8*)p; }
+__device__ __forceinline__ uint32_t lds_cell(uint32_t cell0, uint32_t p, uint32_t wh) {
+    const uint32_t a = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, p), __builtin_bit_cast(u16x2, wh), cell0, false);
+    return *(lds_u8*)(uintptr_t)a;
+}
+
 // The Philox blocks of a group that depend on no state (contract v5: FUEL every step;
 // GATE, whose words are the same whether or not an env consumes them; LOSS_0, the
 // block of the quad's first firing env, used by most waves): drawn right after the
@@ -1190,8 +1211,15 @@ __device__ __forceinline__ uint32_t record_group(const StepArgs& A, int64_t base
 // action's checks as one bit instead of the error code; *O is not touched. Position, origin
 // and dest are read from and written to *U, one register per env, instead of G's packed
 // bytes, so consecutive lean steps neither unpack nor pack them; fuel, cargo and the action
-// stay in G. The state arithmetic, its order, the LDS lookups that feed it and every Philox
-// counter are the full step's.
+// stay in G. The state arithmetic, its order and every Philox counter are the full step's.
+// What the mode does not repeat per step: the cell code under the ship is carried in *U (after
+// a move it is the byte the ground test read at the cell moved to), so a step makes one cell
+// lookup per env, not two; the take checks read the stocks by that code from U->take
+// (stock_by_code: zeros off a port, so `0 < amount <= stock` needs no at-port test and no
+// clamp); the complements of the action-range compares are s_not of their lane masks
+// (with_complement); the cell table's LDS address rides in the dot product (lds_cell); and the
+// caller draws FUEL and GATE together (philox.h, draw2) with their step-invariant parts
+// computed before the loop.
 struct StepOut {
     float rw[4];
     uint32_t dn, ee;  // done / err of the group, packed u8 x4
@@ -1199,6 +1227,8 @@ struct StepOut {
 struct Carried {
     uint32_t pos[4];  // x | y << 16
     int org[4], dst[4];
+    uint32_t code[4];   // the cell code under the ship, w.cell[cell_of(pos)]
+    const int2* take;   // the block's stocks by cell code (stock_by_code), the same for every env
 };
 template <bool kAuto, bool kFull, bool kNt, bool kRec = false, bool kReplay = false, bool kKeep = false,
           bool kLean = false>
@@ -1234,8 +1264,18 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
         // utils/preprocessing.py:111-137: [0,4) moves N, E, S, W (-4..-1 wrap like a
         // Python index), [4, 4+P) SELECT, [4+P, 54+P) TAKE_CARGO, then TAKE_FUEL
         const int act = G.a[j];
-        const bool bad = act < -4, is_mv = act < 4, lt_sel = act < 4 + P, lt_tc = act < 54 + P;
-        val[j] = act - 4 - (lt_sel ? 0 : P) - (lt_tc ? 0 : 50);
+        const bool bad = act < -4;
+        bool is_mv, not_mv, lt_sel, ge_sel;
+        if constexpr (kLean) {
+            const Pred2 mv = with_complement(act < 4), sel = with_complement(act < 4 + P);
+            is_mv = mv.t, not_mv = mv.f, lt_sel = sel.t, ge_sel = sel.f;
+        } else {
+            is_mv = act < 4, lt_sel = act < 4 + P, not_mv = !is_mv, ge_sel = !lt_sel;
+        }
+        const bool lt_tc = act < 54 + P;
+        // kLean: the same value (two's complement) as one subtraction of a selected offset
+        if constexpr (kLean) val[j] = act - (lt_sel ? 4 : lt_tc ? 4 + P : 54 + P);
+        else val[j] = act - 4 - (lt_sel ? 0 : P) - (lt_tc ? 0 : 50);
         const uint32_t dxy = w.moves[act & 3];
         // packed position x | y << 16 from the group's x and y bytes
         uint32_t p;
@@ -1252,26 +1292,39 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
         const bool inb = pk_min_u16(np, lim) == np;  // _is_within_map (:284); -1 wraps to 0xffff
         const bool nodest = dst[j] == SE_NONE;       // :276
         const uint32_t cp = (!nodest & inb) ? np : p;  // in-range cell for the lookups
-        const bool ground = w.cell[cell_of(cp, wh)] == kCellGround;  // :293
+        uint32_t code_cp;
+        if constexpr (kLean) {
+            code_cp = lds_cell(lds_address(w.cell), cp, wh);
+            // carried as a full register (as a byte it is masked again before every select)
+            asm("" : "+v"(code_cp));
+        } else {
+            code_cp = w.cell[cell_of(cp, wh)];
+        }
+        const bool ground = code_cp == kCellGround;  // :293
         pd16[j] = w.pos[min((uint32_t)dst[j], pm1)];
         [[maybe_unused]] bool closer = false;  // old vs ATTEMPTED cell (:307-315)
         if constexpr (!kLean) closer = dist2(p, pd16[j]) > dist2(cp, pd16[j]);
         // TAKE_* (:341-357) at the port on the ship's cell; SELECT_PORT (:265-271)
-        const int k = (int)w.cell[cell_of(p, wh)] - 1;
-        const bool atport = (uint32_t)k < (uint32_t)P;
-        const int2 st2 = w.stock[min((uint32_t)k, pm1)];
-        const int stock = lt_tc ? st2.y : st2.x;
-        const bool amount_bad = (val[j] <= 0) | (val[j] > stock);
-        const bool same = (kLean ? U->org[j] : byte_of(G.org, j)) == val[j];
         bool ok;
         if constexpr (kLean) {
             // the cascade below as its one bit: no check of the action's own type failed
-            // (mask arithmetic, no ?: : a branch here would take the LDS lookups with it)
+            // (mask arithmetic, no ?: : a branch here would take the LDS lookups with it).
+            // The ship's cell code is carried, and the stocks come by that code, zero off a
+            // port: 0 < val <= stock then holds at a port with the stock only.
+            const int2 st2 = U->take[U->code[j]];
+            const int stock = lt_tc ? st2.y : st2.x;
+            const bool same = U->org[j] == val[j];
             const bool ok_mv = is_mv & !nodest & inb;
-            const bool ok_sel = !is_mv & lt_sel & !same;
-            const bool ok_take = !lt_sel & atport & !amount_bad;
+            const bool ok_sel = not_mv & lt_sel & !same;
+            const bool ok_take = ge_sel & (val[j] > 0) & (val[j] <= stock);
             ok = !bad & (P != 0) & (ok_mv | ok_sel | ok_take);
         } else {
+            const int k = (int)w.cell[cell_of(p, wh)] - 1;
+            const bool atport = (uint32_t)k < (uint32_t)P;
+            const int2 st2 = w.stock[min((uint32_t)k, pm1)];
+            const int stock = lt_tc ? st2.y : st2.x;
+            const bool amount_bad = (val[j] <= 0) | (val[j] > stock);
+            const bool same = byte_of(G.org, j) == val[j];
             const int e_move = nodest ? SE_ERR_NO_DEST : (inb ? SE_ERR_OK : SE_ERR_OOB);
             const int e_sel = same ? SE_ERR_SAME_PORT : SE_ERR_OK;
             const int e_amt = amount_bad ? SE_ERR_AMOUNT : SE_ERR_OK;
@@ -1284,11 +1337,12 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
         }
         do_move[j] = ok & is_mv;
         moved[j] = do_move[j] & !ground;
-        const bool take_ok = ok & !lt_sel;
+        const bool take_ok = ok & ge_sel;
         tf_ok[j] = take_ok & !lt_tc;
         const bool tc_ok = take_ok & lt_tc;
-        const bool sel_ok = ok & !is_mv & lt_sel;
+        const bool sel_ok = ok & not_mv & lt_sel;
         pos[j] = moved[j] ? cp : p;
+        if constexpr (kLean) U->code[j] = moved[j] ? code_cp : U->code[j];  // the ground test's read
         cg[j] = tc_ok ? cg[j] + val[j] : cg[j];
         dst[j] = sel_ok ? val[j] : dst[j];
         // reward row before loss / arrival: a move by (out_of_fuel, ground, closer),
@@ -1874,6 +1928,18 @@ __global__ __launch_bounds__(64) void step_tail_kernel(StepArgs A) {
     step_tail_envs<kTyped, kReplay, kAuto>(A, world_view(A.dims, A.world));
 }
 
+// The stocks by cell code for the state-only steps' take checks: 256 (fuel, cargo) pairs,
+// port i's at code i + 1 and zeros at every other code (0 water, kCellGround, codes past P),
+// so `0 < amount <= stock` is false wherever the ship is on no port. One entry per thread of
+// the block, read from the staged image; the caller holds the barrier.
+constexpr size_t kStockByCodeBytes = 256 * sizeof(int2);
+static_assert(kStepBlock == 256, "stock_by_code: one cell code per thread");
+__device__ __forceinline__ void stock_by_code(const LdsWorld& w, int2* take) {
+    const uint32_t k = threadIdx.x - 1u, P = (uint32_t)w.P;
+    const int2 s = w.stock[min(k, P > 0 ? P - 1 : 0u)];  // P = 0: a word of the image, unused
+    take[threadIdx.x] = k < P ? s : make_int2(0, 0);
+}
+
 // se_step_seq without auto-reset, fused: `steps` consecutive steps of the agent path in one
 // launch, on step_kernel's grid and ownership. Nothing outside the stream can observe the
 // state between two steps of one sequence, and a step reads only x, y, origin, dest, cargo,
@@ -1907,13 +1973,25 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
     }
     __builtin_amdgcn_sched_barrier(0);
     const LdsWorld w = stage_finish(A.world, A.dims, lds, st);
+    // the state-only steps' take checks: the stocks by cell code, behind the staged image
+    int2* const take = reinterpret_cast<int2*>(lds + A.dims.padded());
+    if (steps > 1) {  // launch-uniform
+        stock_by_code(w, take);
+        __syncthreads();
+    }
 
     BlockStats bs;
     Finished F;
     for (int64_t i = 0; i < A.iters; ++i) {
         const int64_t g0 = first + i * kStepBlock, g = g0 + threadIdx.x;
         if (g >= full) break;  // no barrier below
-        if (i > 0) G.template load<true>(A, At<true>{g0, 0, A.n});
+        if (i > 0) {
+            // the lane opaque: the loads' per-lane addresses are computed here, once per group,
+            // not kept in ~20 VGPRs across the step loop for the next group's sake
+            uint32_t lane = threadIdx.x;
+            asm volatile("" : "+v"(lane));
+            G.template load<true>(A, At<true>{g0, 0, A.n}, lane);
+        }
         const At<true> at{g0, g * 4, A.n};
         const uint32_t tl = A.t + (uint32_t)(steps - 1);  // the last step's counter
         if (steps > 1) {
@@ -1924,14 +2002,22 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                 U.pos[j] = __builtin_amdgcn_perm(G.y, G.x, (uint32_t)j | 0x0c000c00u | ((uint32_t)(4 + j) << 16));
                 U.org[j] = byte_of(G.org, j);
                 U.dst[j] = byte_of(G.dst, j);
+                U.code[j] = w.cell[cell_of(U.pos[j], (uint32_t)w.W | (1u << 16))];
             }
+            U.take = take;
+            // the step-invariant parts of the quad's FUEL and GATE blocks (philox.h, draw2),
+            // opaque so the loop keeps them in registers as computed here
+            const Key qk = env_key(A.seed, (A.env_base + g * 4) >> 2);
+            PairInv inv = pair_invariants(qk);
+            asm volatile("" : "+v"(inv.hi[0]), "+v"(inv.lo[0]), "+v"(inv.hi[1]), "+v"(inv.lo[1]));
             const int32_t* row = A.act;
             for (uint32_t t = A.t; t != tl; ++t) {
                 // the next row's actions (there is one: the last step follows)
                 row += ld;
                 int32_t nxt[4];
                 ld4_full<kNt>(row, g0, nxt);
-                const Draws D = early_draws<false>(A, g * 4, t);
+                const U4x2 fg = draw2(qk, inv, t);
+                const Draws D{fg.fuel, fg.gate, U4{{0u, 0u, 0u, 0u}}, U4{{0u, 0u, 0u, 0u}}};
                 step_group_agent<false, true, kNt, false, false, true, true>(A, w, G, at, bs, F, D, t, nullptr, &U);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
@@ -2940,8 +3026,9 @@ int launch_step_seq(se_env* env, const int32_t* act, int64_t ld, int32_t steps, 
     A.iters = env->iters;
     const hipStream_t s = (hipStream_t)stream;
     if (env->n >= kEnvsPerThread) {  // at least one full group (the kernel's first load assumes it)
-        if (env->nt_loads) step_seq_kernel<true><<<env->grid, kStepBlock, lds_bytes(env), s>>>(A, steps, ld);
-        else step_seq_kernel<false><<<env->grid, kStepBlock, lds_bytes(env), s>>>(A, steps, ld);
+        const size_t lds = lds_bytes(env) + kStockByCodeBytes;  // the image, then stock_by_code's table
+        if (env->nt_loads) step_seq_kernel<true><<<env->grid, kStepBlock, lds, s>>>(A, steps, ld);
+        else step_seq_kernel<false><<<env->grid, kStepBlock, lds, s>>>(A, steps, ld);
         HIP_TRY(hipGetLastError());
     }
     if (env->n & 3) {
@@ -3102,7 +3189,10 @@ int se_step_seq_mark(se_env* env, const int32_t* actions, int64_t ld, int32_t st
     // without auto-reset nothing reads the state between two steps of the run: fused launches
     // (step_seq_kernel), split where the event goes and at seq_max_steps. Auto-reset keeps a
     // launch per step (its done lists and statistics are per step).
-    const bool fused = env->seq_fuse && env->n > 0 && !(env->flags & SE_FLAG_AUTO_RESET);
+    // A world image that fills the 64 KiB a launch can ask for leaves no room for the fused
+    // kernel's stock table: such an env steps per launch, as step_kernel still fits.
+    const bool fused = env->seq_fuse && env->n > 0 && !(env->flags & SE_FLAG_AUTO_RESET) &&
+                       lds_bytes(env) + kStockByCodeBytes <= (size_t)64 * 1024;
     for (int32_t k = 0; k <= steps;) {
         if (event && k == mark_after) {
             DeviceGuard g(env->device);
