@@ -1220,6 +1220,10 @@ __device__ __forceinline__ uint32_t record_group(const StepArgs& A, int64_t base
 // (with_complement); the cell table's LDS address rides in the dot product (lds_cell); and the
 // caller draws FUEL and GATE together (philox.h, draw2) with their step-invariant parts
 // computed before the loop.
+// What the mode does only for a wave that needs it (two ballots per step, scalar branches): the
+// take, when an env of the wave has a take action on a non-water cell, and the arrival test,
+// when a mover of the wave stands on a non-water cell after its move. Ships are mostly at sea,
+// so most wave-steps run neither (profiles/seq_guard/freq.json).
 struct StepOut {
     float rw[4];
     uint32_t dn, ee;  // done / err of the group, packed u8 x4
@@ -1259,6 +1263,35 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
     [[maybe_unused]] int err[4], ridx[4];  // not in the state-only step
     bool do_move[4], moved[4], tf_ok[4];
     bool gate_needed = false;
+    if constexpr (kLean) {
+        // The take guard. A take passes only for a ship on a port cell, so a wave none of whose
+        // envs has a take action on a non-water cell (code != 0: wider than "a port's code", so
+        // ground and codes past P only send their wave here) skips the whole take: the stock
+        // read, the amount checks, the cargo add and the fuel's f64 conversion. The vote is a
+        // ballot, so the branch is scalar; it reads this step's actions and the codes before
+        // the move. A passed take changes only cargo and fuel, and its env neither moves nor
+        // selects, so it is applied to G here and the step below runs without it: cargo is
+        // what `tc_ok ? cargo + amount : cargo` gave, and fuel reaches the fuel update as
+        // G.f + amount, to which that update adds -0.0, which changes no bit of any value.
+        bool take_any = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) take_any |= (G.a[j] >= 4 + P) & (U->code[j] != 0);
+        if (__builtin_amdgcn_ballot_w64(take_any) != 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int act = G.a[j];
+                const bool lt_tc = act < 54 + P;
+                const int amount = act - (lt_tc ? 4 + P : 54 + P);
+                // the stocks by the carried cell code, zero off a port: 0 < amount <= stock
+                // then holds at a port with the stock only (and never when P == 0)
+                const int2 st2 = U->take[U->code[j]];
+                const int stock = lt_tc ? st2.y : st2.x;
+                const bool ok_take = (act >= 4 + P) & (amount > 0) & (amount <= stock);
+                G.c[j] = (ok_take & lt_tc) ? G.c[j] + amount : G.c[j];
+                G.f[j] = (ok_take & !lt_tc) ? G.f[j] + (double)amount : G.f[j];
+            }
+        }
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         // utils/preprocessing.py:111-137: [0,4) moves N, E, S, W (-4..-1 wrap like a
@@ -1272,9 +1305,9 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
         } else {
             is_mv = act < 4, lt_sel = act < 4 + P, not_mv = !is_mv, ge_sel = !lt_sel;
         }
-        const bool lt_tc = act < 54 + P;
-        // kLean: the same value (two's complement) as one subtraction of a selected offset
-        if constexpr (kLean) val[j] = act - (lt_sel ? 4 : lt_tc ? 4 + P : 54 + P);
+        [[maybe_unused]] const bool lt_tc = act < 54 + P;
+        // kLean: the takes are done (the take guard above), and only a select reads the value
+        if constexpr (kLean) val[j] = act - 4;
         else val[j] = act - 4 - (lt_sel ? 0 : P) - (lt_tc ? 0 : 50);
         const uint32_t dxy = w.moves[act & 3];
         // packed position x | y << 16 from the group's x and y bytes
@@ -1301,23 +1334,22 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
             code_cp = w.cell[cell_of(cp, wh)];
         }
         const bool ground = code_cp == kCellGround;  // :293
-        pd16[j] = w.pos[min((uint32_t)dst[j], pm1)];
         [[maybe_unused]] bool closer = false;  // old vs ATTEMPTED cell (:307-315)
-        if constexpr (!kLean) closer = dist2(p, pd16[j]) > dist2(cp, pd16[j]);
+        if constexpr (!kLean) {  // kLean: the destination's position only behind the arrival guard
+            pd16[j] = w.pos[min((uint32_t)dst[j], pm1)];
+            closer = dist2(p, pd16[j]) > dist2(cp, pd16[j]);
+        }
         // TAKE_* (:341-357) at the port on the ship's cell; SELECT_PORT (:265-271)
         bool ok;
         if constexpr (kLean) {
             // the cascade below as its one bit: no check of the action's own type failed
             // (mask arithmetic, no ?: : a branch here would take the LDS lookups with it).
-            // The ship's cell code is carried, and the stocks come by that code, zero off a
-            // port: 0 < val <= stock then holds at a port with the stock only.
-            const int2 st2 = U->take[U->code[j]];
-            const int stock = lt_tc ? st2.y : st2.x;
+            // A take is not among them: the take guard has applied it, and nothing below
+            // reads whether a take passed.
             const bool same = U->org[j] == val[j];
             const bool ok_mv = is_mv & !nodest & inb;
             const bool ok_sel = not_mv & lt_sel & !same;
-            const bool ok_take = ge_sel & (val[j] > 0) & (val[j] <= stock);
-            ok = !bad & (P != 0) & (ok_mv | ok_sel | ok_take);
+            ok = !bad & (P != 0) & (ok_mv | ok_sel);
         } else {
             const int k = (int)w.cell[cell_of(p, wh)] - 1;
             const bool atport = (uint32_t)k < (uint32_t)P;
@@ -1337,7 +1369,7 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
         }
         do_move[j] = ok & is_mv;
         moved[j] = do_move[j] & !ground;
-        const bool take_ok = ok & ge_sel;
+        const bool take_ok = kLean ? false : ok & ge_sel;
         tf_ok[j] = take_ok & !lt_tc;
         const bool tc_ok = take_ok & lt_tc;
         const bool sel_ok = ok & not_mv & lt_sel;
@@ -1358,6 +1390,22 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
     const U4 fb = D.fuel;
     const U4 gb = D.gate;
     uint32_t fire = 0, arrive = 0, fin = 0, dead = 0;
+    if constexpr (kLean) {
+        // The arrival guard. An arrival (:325) happens on a port's cell, and the world image
+        // stamps every port's cell with a non-zero code, so a wave none of whose movers is on
+        // a non-water cell after the move has no arrival and reads no destination position.
+        // The vote is a ballot (a scalar branch) over the codes as the move left them. The
+        // test itself stays the position compare: two ports may share a cell, and dest may
+        // hold anything a caller loaded. (A mover selects nothing, so dst is still its dest.)
+        bool arrive_any = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) arrive_any |= do_move[j] & (U->code[j] != 0);
+        if (__builtin_amdgcn_ballot_w64(arrive_any) != 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                arrive |= (uint32_t)(do_move[j] & (pos[j] == w.pos[min((uint32_t)dst[j], pm1)])) << j;
+        }
+    }
     double f[4];
     [[maybe_unused]] double r[4];  // not in the state-only step
     // kReplay: the group's tape records (the partial last group's missing envs read none)
@@ -1400,8 +1448,8 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
         }
         if constexpr (!kLean) r[j] = w.rtab[ridx[j] | ((int)(do_move[j] & oof) << 2)];
         fire |= (uint32_t)fires << j;
-        arrive |= (uint32_t)(do_move[j] & (pos[j] == pd16[j])) << j;  // :325
         if constexpr (!kLean) {
+            arrive |= (uint32_t)(do_move[j] & (pos[j] == pd16[j])) << j;  // :325
             dead |= (uint32_t)(do_move[j] & oof) << j;
             fin |= (uint32_t)((kFull || base + j < n) & do_move[j] & oof) << j;
         }
