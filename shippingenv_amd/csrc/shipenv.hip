@@ -1124,6 +1124,17 @@ __device__ __forceinline__ Draws early_draws(const StepArgs& A, int64_t base) {
 template <bool kAuto>
 constexpr bool spec_loss() { return kAuto; }
 
+// The group's x and y bytes (packed u8 x4) and its positions, one register x | y << 16 per env.
+__device__ __forceinline__ uint32_t unpack_pos(uint32_t x4, uint32_t y4, int j) {
+    return __builtin_amdgcn_perm(y4, x4, (uint32_t)j | 0x0c000c00u | ((uint32_t)(4 + j) << 16));
+}
+__device__ __forceinline__ void pack_pos(const uint32_t (&pos)[4], uint32_t& x4, uint32_t& y4) {
+    const uint32_t t01 = __builtin_amdgcn_perm(pos[1], pos[0], 0x06020400u);  // x0 x1 y0 y1
+    const uint32_t t23 = __builtin_amdgcn_perm(pos[3], pos[2], 0x06020400u);  // x2 x3 y2 y3
+    x4 = __builtin_amdgcn_perm(t23, t01, 0x05040100u);
+    y4 = __builtin_amdgcn_perm(t23, t01, 0x07060302u);
+}
+
 // se_step_record, per group of 4 envs at env index base (a full group; head and cap
 // multiples of 4, so its ring slots are consecutive): the stores of replay_end4_kernel
 // (csrc/replay.h) from the post-step values this thread just computed. After the
@@ -1202,49 +1213,18 @@ __device__ __forceinline__ uint32_t record_group(const StepArgs& A, int64_t base
 // caller stores the state and the last step's outputs once. The arithmetic is the per-step
 // code's, untouched. (tk and O are trailing defaults, not a wrapper: the per-step
 // instantiations then compile to the instructions they had before.)
-//
-// kLean (with kKeep only: the steps of a fused sequence before its last): the state-only
-// step. Nothing can read an inner step's reward, done or err, and without auto-reset the next
-// state needs neither the out-of-fuel flag (a dead ship keeps moving) nor which error was
-// raised, only whether one was. So the mode computes no reward (no closer test, no reward
-// table read, no f64 loss / arrival adds, no f32 conversion), no out-of-fuel compare, and the
-// action's checks as one bit instead of the error code; *O is not touched. Position, origin
-// and dest are read from and written to *U, one register per env, instead of G's packed
-// bytes, so consecutive lean steps neither unpack nor pack them; fuel, cargo and the action
-// stay in G. The state arithmetic, its order and every Philox counter are the full step's.
-// What the mode does not repeat per step: the cell code under the ship is carried in *U (after
-// a move it is the byte the ground test read at the cell moved to), so a step makes one cell
-// lookup per env, not two; the take checks read the stocks by that code from U->take
-// (stock_by_code: zeros off a port, so `0 < amount <= stock` needs no at-port test and no
-// clamp); the complements of the action-range compares are s_not of their lane masks
-// (with_complement); the cell table's LDS address rides in the dot product (lds_cell); and the
-// caller draws FUEL and GATE together (philox.h, draw2) with their step-invariant parts
-// computed before the loop.
-// What the mode does only for a wave that needs it (two ballots per step, scalar branches): the
-// take, when an env of the wave has a take action on a non-water cell, and the arrival test,
-// when a mover of the wave stands on a non-water cell after its move. Ships are mostly at sea,
-// so most wave-steps run neither (profiles/seq_guard/freq.json).
 struct StepOut {
     float rw[4];
     uint32_t dn, ee;  // done / err of the group, packed u8 x4
 };
-struct Carried {
-    uint32_t pos[4];  // x | y << 16
-    int org[4], dst[4];
-    uint32_t code[4];   // the cell code under the ship, w.cell[cell_of(pos)]
-    const int2* take;   // the block's stocks by cell code (stock_by_code), the same for every env
-};
-template <bool kAuto, bool kFull, bool kNt, bool kRec = false, bool kReplay = false, bool kKeep = false,
-          bool kLean = false>
+template <bool kAuto, bool kFull, bool kNt, bool kRec = false, bool kReplay = false, bool kKeep = false>
 __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWorld& w,
                                                  Group<false, kAuto, kNt>& G, At<kFull> at,
                                                  BlockStats& bs, Finished& F, const Draws& D,
                                                  [[maybe_unused]] uint32_t tk = 0,
-                                                 [[maybe_unused]] StepOut* O = nullptr,
-                                                 [[maybe_unused]] Carried* U = nullptr) {
+                                                 [[maybe_unused]] StepOut* O = nullptr) {
     static_assert(!kReplay || (!kAuto && !kRec), "agent replay: no auto-reset, no ring record");
     static_assert(!kKeep || (kFull && !kAuto && !kRec && !kReplay), "fused sequence: full groups, no auto-reset");
-    static_assert(!kLean || kKeep, "state-only step: only inside a fused sequence (kKeep), whose last step is a full one");
     const int64_t n = A.n, base = at.base;
     const int P = w.P;
     const uint32_t lim = (uint32_t)(w.H - 1) | ((uint32_t)(w.W - 1) << 16);
@@ -1259,155 +1239,68 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
 #endif
     // --- first half: everything that needs no optional draw (:359-376, :273-315)
     uint32_t pos[4], pd16[4];
-    int val[4], dst[4], cg[4];
-    [[maybe_unused]] int err[4], ridx[4];  // not in the state-only step
+    int val[4], dst[4], cg[4], err[4], ridx[4];
     bool do_move[4], moved[4], tf_ok[4];
     bool gate_needed = false;
-    if constexpr (kLean) {
-        // The take guard. A take passes only for a ship on a port cell, so a wave none of whose
-        // envs has a take action on a non-water cell (code != 0: wider than "a port's code", so
-        // ground and codes past P only send their wave here) skips the whole take: the stock
-        // read, the amount checks, the cargo add and the fuel's f64 conversion. The vote is a
-        // ballot, so the branch is scalar; it reads this step's actions and the codes before
-        // the move. A passed take changes only cargo and fuel, and its env neither moves nor
-        // selects, so it is applied to G here and the step below runs without it: cargo is
-        // what `tc_ok ? cargo + amount : cargo` gave, and fuel reaches the fuel update as
-        // G.f + amount, to which that update adds -0.0, which changes no bit of any value.
-        bool take_any = false;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) take_any |= (G.a[j] >= 4 + P) & (U->code[j] != 0);
-        if (__builtin_amdgcn_ballot_w64(take_any) != 0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int act = G.a[j];
-                const bool lt_tc = act < 54 + P;
-                const int amount = act - (lt_tc ? 4 + P : 54 + P);
-                // the stocks by the carried cell code, zero off a port: 0 < amount <= stock
-                // then holds at a port with the stock only (and never when P == 0)
-                const int2 st2 = U->take[U->code[j]];
-                const int stock = lt_tc ? st2.y : st2.x;
-                const bool ok_take = (act >= 4 + P) & (amount > 0) & (amount <= stock);
-                G.c[j] = (ok_take & lt_tc) ? G.c[j] + amount : G.c[j];
-                G.f[j] = (ok_take & !lt_tc) ? G.f[j] + (double)amount : G.f[j];
-            }
-        }
-    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         // utils/preprocessing.py:111-137: [0,4) moves N, E, S, W (-4..-1 wrap like a
         // Python index), [4, 4+P) SELECT, [4+P, 54+P) TAKE_CARGO, then TAKE_FUEL
         const int act = G.a[j];
         const bool bad = act < -4;
-        bool is_mv, not_mv, lt_sel, ge_sel;
-        if constexpr (kLean) {
-            const Pred2 mv = with_complement(act < 4), sel = with_complement(act < 4 + P);
-            is_mv = mv.t, not_mv = mv.f, lt_sel = sel.t, ge_sel = sel.f;
-        } else {
-            is_mv = act < 4, lt_sel = act < 4 + P, not_mv = !is_mv, ge_sel = !lt_sel;
-        }
-        [[maybe_unused]] const bool lt_tc = act < 54 + P;
-        // kLean: the takes are done (the take guard above), and only a select reads the value
-        if constexpr (kLean) val[j] = act - 4;
-        else val[j] = act - 4 - (lt_sel ? 0 : P) - (lt_tc ? 0 : 50);
+        const bool is_mv = act < 4, lt_sel = act < 4 + P, lt_tc = act < 54 + P;
+        val[j] = act - 4 - (lt_sel ? 0 : P) - (lt_tc ? 0 : 50);
         const uint32_t dxy = w.moves[act & 3];
-        // packed position x | y << 16 from the group's x and y bytes
-        uint32_t p;
-        if constexpr (kLean) {
-            p = U->pos[j];
-            dst[j] = U->dst[j];
-        } else {
-            p = __builtin_amdgcn_perm(G.y, G.x, (uint32_t)j | 0x0c000c00u | ((uint32_t)(4 + j) << 16));
-            dst[j] = byte_of(G.dst, j);
-        }
+        const uint32_t p = unpack_pos(G.x, G.y, j);
+        dst[j] = byte_of(G.dst, j);
         cg[j] = G.c[j];
         // MOVE (_move_ship :273-339)
         const uint32_t np = pk_add_u16(p, dxy);
         const bool inb = pk_min_u16(np, lim) == np;  // _is_within_map (:284); -1 wraps to 0xffff
         const bool nodest = dst[j] == SE_NONE;       // :276
         const uint32_t cp = (!nodest & inb) ? np : p;  // in-range cell for the lookups
-        uint32_t code_cp;
-        if constexpr (kLean) {
-            code_cp = lds_cell(lds_address(w.cell), cp, wh);
-            // carried as a full register (as a byte it is masked again before every select)
-            asm("" : "+v"(code_cp));
-        } else {
-            code_cp = w.cell[cell_of(cp, wh)];
-        }
-        const bool ground = code_cp == kCellGround;  // :293
-        [[maybe_unused]] bool closer = false;  // old vs ATTEMPTED cell (:307-315)
-        if constexpr (!kLean) {  // kLean: the destination's position only behind the arrival guard
-            pd16[j] = w.pos[min((uint32_t)dst[j], pm1)];
-            closer = dist2(p, pd16[j]) > dist2(cp, pd16[j]);
-        }
+        const bool ground = w.cell[cell_of(cp, wh)] == kCellGround;  // :293
+        pd16[j] = w.pos[min((uint32_t)dst[j], pm1)];
+        const bool closer = dist2(p, pd16[j]) > dist2(cp, pd16[j]);  // old vs ATTEMPTED cell (:307-315)
         // TAKE_* (:341-357) at the port on the ship's cell; SELECT_PORT (:265-271)
-        bool ok;
-        if constexpr (kLean) {
-            // the cascade below as its one bit: no check of the action's own type failed
-            // (mask arithmetic, no ?: : a branch here would take the LDS lookups with it).
-            // A take is not among them: the take guard has applied it, and nothing below
-            // reads whether a take passed.
-            const bool same = U->org[j] == val[j];
-            const bool ok_mv = is_mv & !nodest & inb;
-            const bool ok_sel = not_mv & lt_sel & !same;
-            ok = !bad & (P != 0) & (ok_mv | ok_sel);
-        } else {
-            const int k = (int)w.cell[cell_of(p, wh)] - 1;
-            const bool atport = (uint32_t)k < (uint32_t)P;
-            const int2 st2 = w.stock[min((uint32_t)k, pm1)];
-            const int stock = lt_tc ? st2.y : st2.x;
-            const bool amount_bad = (val[j] <= 0) | (val[j] > stock);
-            const bool same = byte_of(G.org, j) == val[j];
-            const int e_move = nodest ? SE_ERR_NO_DEST : (inb ? SE_ERR_OK : SE_ERR_OOB);
-            const int e_sel = same ? SE_ERR_SAME_PORT : SE_ERR_OK;
-            const int e_amt = amount_bad ? SE_ERR_AMOUNT : SE_ERR_OK;
-            const int e_take = atport ? e_amt : SE_ERR_NOT_AT_PORT;
-            const int e_ns = lt_sel ? e_sel : e_take;
-            const int e_ty = is_mv ? e_move : e_ns;
-            const int e_p = P == 0 ? SE_ERR_NO_PORTS : e_ty;  // :360
-            err[j] = bad ? SE_ERR_BAD_INDEX : e_p;            // the decode runs before env.step
-            ok = err[j] == SE_ERR_OK;
-        }
+        const int k = (int)w.cell[cell_of(p, wh)] - 1;
+        const bool atport = (uint32_t)k < (uint32_t)P;
+        const int2 st2 = w.stock[min((uint32_t)k, pm1)];
+        const int stock = lt_tc ? st2.y : st2.x;
+        const bool amount_bad = (val[j] <= 0) | (val[j] > stock);
+        const bool same = byte_of(G.org, j) == val[j];
+        const int e_move = nodest ? SE_ERR_NO_DEST : (inb ? SE_ERR_OK : SE_ERR_OOB);
+        const int e_sel = same ? SE_ERR_SAME_PORT : SE_ERR_OK;
+        const int e_amt = amount_bad ? SE_ERR_AMOUNT : SE_ERR_OK;
+        const int e_take = atport ? e_amt : SE_ERR_NOT_AT_PORT;
+        const int e_ns = lt_sel ? e_sel : e_take;
+        const int e_ty = is_mv ? e_move : e_ns;
+        const int e_p = P == 0 ? SE_ERR_NO_PORTS : e_ty;  // :360
+        err[j] = bad ? SE_ERR_BAD_INDEX : e_p;            // the decode runs before env.step
+        const bool ok = err[j] == SE_ERR_OK;
         do_move[j] = ok & is_mv;
         moved[j] = do_move[j] & !ground;
-        const bool take_ok = kLean ? false : ok & ge_sel;
+        const bool take_ok = ok & !lt_sel;
         tf_ok[j] = take_ok & !lt_tc;
         const bool tc_ok = take_ok & lt_tc;
-        const bool sel_ok = ok & not_mv & lt_sel;
+        const bool sel_ok = ok & !is_mv & lt_sel;
         pos[j] = moved[j] ? cp : p;
-        if constexpr (kLean) U->code[j] = moved[j] ? code_cp : U->code[j];  // the ground test's read
         cg[j] = tc_ok ? cg[j] + val[j] : cg[j];
         dst[j] = sel_ok ? val[j] : dst[j];
         // reward row before loss / arrival: a move by (out_of_fuel, ground, closer),
         // filled in once fuel is known; a take 0.05; anything else 0
-        if constexpr (!kLean) {
-            const int r_rest = take_ok ? 8 : 9;
-            ridx[j] = do_move[j] ? (((int)ground << 1) | (int)closer) : r_rest;
-        }
+        const int r_rest = take_ok ? 8 : 9;
+        ridx[j] = do_move[j] ? (((int)ground << 1) | (int)closer) : r_rest;
         gate_needed |= !bad & is_mv & !nodest & inb & (G.c[j] > 0) & (G.c[j] < 50);
     }
     TRACE_STAMP(5);
-    (void)gate_needed;  // drawn early (early_draws) whether or not an env needs it
+    // GATE is drawn early (early_draws) whether or not an env needs it. The dead expression
+    // stays: without it the compiler schedules the replay kernel's instructions in another order.
+    (void)gate_needed;
     const U4 fb = D.fuel;
     const U4 gb = D.gate;
     uint32_t fire = 0, arrive = 0, fin = 0, dead = 0;
-    if constexpr (kLean) {
-        // The arrival guard. An arrival (:325) happens on a port's cell, and the world image
-        // stamps every port's cell with a non-zero code, so a wave none of whose movers is on
-        // a non-water cell after the move has no arrival and reads no destination position.
-        // The vote is a ballot (a scalar branch) over the codes as the move left them. The
-        // test itself stays the position compare: two ports may share a cell, and dest may
-        // hold anything a caller loaded. (A mover selects nothing, so dst is still its dest.)
-        bool arrive_any = false;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) arrive_any |= do_move[j] & (U->code[j] != 0);
-        if (__builtin_amdgcn_ballot_w64(arrive_any) != 0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                arrive |= (uint32_t)(do_move[j] & (pos[j] == w.pos[min((uint32_t)dst[j], pm1)])) << j;
-        }
-    }
-    double f[4];
-    [[maybe_unused]] double r[4];  // not in the state-only step
+    double f[4], r[4];
     // kReplay: the group's tape records (the partial last group's missing envs read none)
     [[maybe_unused]] double tu[4], tg[4], tt[4], tb[4];
     [[maybe_unused]] int td[4];
@@ -1430,8 +1323,7 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
         double scale;
         if constexpr (kReplay) scale = 1.0 + (-0.1 + 0.2 * tu[j]);
         else scale = 1.0 + (-0.1 + (double)fb.v[j] * kFifthPerWord);
-        [[maybe_unused]] bool oof = false;  // :288-290 (the ship still moves)
-        if constexpr (!kLean) oof = G.f[j] < scale;
+        const bool oof = G.f[j] < scale;  // :288-290 (the ship still moves)
         const double take = tf_ok[j] ? (double)val[j] : -0.0;
         f[j] = G.f[j] + (moved[j] ? -scale : take);
         // the gate random() <= cargo / 50 (:318-323) as w <= floor(fl(c/50) 2^32); the
@@ -1446,21 +1338,18 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
             const uint32_t thr = w.gate_thr[min(max(cg[j], 0), 50)];
             fires = do_move[j] & (cg[j] > 0) & (gb.v[j] <= thr);
         }
-        if constexpr (!kLean) r[j] = w.rtab[ridx[j] | ((int)(do_move[j] & oof) << 2)];
+        r[j] = w.rtab[ridx[j] | ((int)(do_move[j] & oof) << 2)];
         fire |= (uint32_t)fires << j;
-        if constexpr (!kLean) {
-            arrive |= (uint32_t)(do_move[j] & (pos[j] == pd16[j])) << j;  // :325
-            dead |= (uint32_t)(do_move[j] & oof) << j;
-            fin |= (uint32_t)((kFull || base + j < n) & do_move[j] & oof) << j;
-        }
+        arrive |= (uint32_t)(do_move[j] & (pos[j] == pd16[j])) << j;  // :325
+        dead |= (uint32_t)(do_move[j] & oof) << j;
+        fin |= (uint32_t)((kFull || base + j < n) & do_move[j] & oof) << j;
     }
     // the flags travel as opaque VGPR bit masks (no lane masks live in SGPR pairs
-    // across the draw blocks below); the state-only step has no dead / fin to keep
-    if constexpr (kLean) asm volatile("" : "+v"(fire), "+v"(arrive));
-    else asm volatile("" : "+v"(fire), "+v"(arrive), "+v"(fin), "+v"(dead));
+    // across the draw blocks below)
+    asm volatile("" : "+v"(fire), "+v"(arrive), "+v"(fin), "+v"(dead));
     int org[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) org[j] = kLean ? U->org[j] : byte_of(G.org, j);
+    for (int j = 0; j < 4; ++j) org[j] = byte_of(G.org, j);
 
     // auto-reset (:227-243) of the envs that ran out of fuel: position and fuel now,
     // cargo / origin / dest after the second half (whose reward the finished episode
@@ -1502,54 +1391,43 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
     }
     // x, y, fuel, done and err are final here (cargo loss and arrival change none)
     uint32_t rec_x = 0, rec_y = 0, rec_cut = 0;
-    if constexpr (kLean) {
+    uint32_t ox, oy, dn = 0, ee = 0;
+    pack_pos(pos, ox, oy);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        dn |= ((dead >> j) & 1u) << (8 * j);
+        ee |= (uint32_t)(err[j] & 0xff) << (8 * j);
+    }
+    if constexpr (kRec) {  // replay_end4_kernel's flags and s' fuel now; x / y held to the end
+        rec_x = ox;
+        rec_y = oy;
+        uint32_t flags4 = 0;
+        float nf[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            U->pos[j] = pos[j];
-            G.f[j] = f[j];
+            const bool raised = err[j] != SE_ERR_OK;
+            nf[j] = (float)f[j];
+            flags4 |= (((dead >> j) & 1u ? (uint32_t)kRecDone : 0u) | (raised ? (uint32_t)kRecInvalid : 0u)) << (8 * j);
+            rec_cut |= (uint32_t)raised << (8 * j);
         }
+        record_early(late_args(), base, flags4, nf);
+    }
+    if constexpr (kKeep) {
+        G.x = ox;
+        G.y = oy;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) G.f[j] = f[j];
+        O->dn = dn;
+        O->ee = ee;
     } else {
-        const uint32_t t01 = __builtin_amdgcn_perm(pos[1], pos[0], 0x06020400u);  // x0 x1 y0 y1
-        const uint32_t t23 = __builtin_amdgcn_perm(pos[3], pos[2], 0x06020400u);  // x2 x3 y2 y3
-        const uint32_t ox = __builtin_amdgcn_perm(t23, t01, 0x05040100u);
-        const uint32_t oy = __builtin_amdgcn_perm(t23, t01, 0x07060302u);
-        uint32_t dn = 0, ee = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            dn |= ((dead >> j) & 1u) << (8 * j);
-            ee |= (uint32_t)(err[j] & 0xff) << (8 * j);
-        }
-        if constexpr (kRec) {  // replay_end4_kernel's flags and s' fuel now; x / y held to the end
-            rec_x = ox;
-            rec_y = oy;
-            uint32_t flags4 = 0;
-            float nf[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bool raised = err[j] != SE_ERR_OK;
-                nf[j] = (float)f[j];
-                flags4 |= (((dead >> j) & 1u ? (uint32_t)kRecDone : 0u) | (raised ? (uint32_t)kRecInvalid : 0u)) << (8 * j);
-                rec_cut |= (uint32_t)raised << (8 * j);
-            }
-            record_early(late_args(), base, flags4, nf);
-        }
-        if constexpr (kKeep) {
-            G.x = ox;
-            G.y = oy;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) G.f[j] = f[j];
-            O->dn = dn;
-            O->ee = ee;
-        } else {
-            const se_state& S = A.st;
-            __builtin_amdgcn_sched_barrier(0);  // the fuel halves back to back (store_moved)
-            store4u8(S.x, at, ox);
-            store4u8(S.y, at, oy);
-            store4(S.fuel, at, f);
-            store4u8(S.done, at, dn);
-            store4u8(reinterpret_cast<uint8_t*>(S.err), at, ee);
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        const se_state& S = A.st;
+        __builtin_amdgcn_sched_barrier(0);  // the fuel halves back to back (store_moved)
+        store4u8(S.x, at, ox);
+        store4u8(S.y, at, oy);
+        store4(S.fuel, at, f);
+        store4u8(S.done, at, dn);
+        store4u8(reinterpret_cast<uint8_t*>(S.err), at, ee);
+        __builtin_amdgcn_sched_barrier(0);
     }
     TRACE_STAMP(6);
 
@@ -1609,10 +1487,8 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
             const int some = lt[j] > kTypeHi ? cg[j] : part;
             const int loss = lt[j] < kTypeLo ? 0 : some;
             const bool fj = (fire >> j) & 1u;
-            if constexpr (!kLean) {
-                const double rl = r[j] + (double)loss * -3.0;  // int(loss * -3) exactly, then += (:323)
-                r[j] = fj ? rl : r[j];
-            }
+            const double rl = r[j] + (double)loss * -3.0;  // int(loss * -3) exactly, then += (:323)
+            r[j] = fj ? rl : r[j];
             cg[j] = fj ? cg[j] - loss : cg[j];
         }
     }
@@ -1623,8 +1499,7 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const bool aj = (arrive >> j) & 1u;
-            [[maybe_unused]] double ra = 0.0;
-            if constexpr (!kLean) ra = (r[j] + (double)(2 * cg[j])) + 10.0;
+            const double ra = (r[j] + (double)(2 * cg[j])) + 10.0;
             int nd;
             if constexpr (kReplay) {
                 nd = td[j];
@@ -1632,20 +1507,11 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
             } else {
                 nd = pick_other(ab.v[j], P, dst[j]);
             }
-            if constexpr (!kLean) r[j] = aj ? ra : r[j];
+            r[j] = aj ? ra : r[j];
             cg[j] = aj ? 0 : cg[j];
             org[j] = aj ? dst[j] : org[j];
             dst[j] = aj ? nd : dst[j];
         }
-    }
-    if constexpr (kLean) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            U->org[j] = org[j];
-            U->dst[j] = dst[j];
-            G.c[j] = cg[j];
-        }
-        return;
     }
     float rw[4], epr[4];
     int32_t epl[4];  // kRec: the running length after this step (0 for a finished episode)
@@ -1976,6 +1842,193 @@ __global__ __launch_bounds__(64) void step_tail_kernel(StepArgs A) {
     step_tail_envs<kTyped, kReplay, kAuto>(A, world_view(A.dims, A.world));
 }
 
+// The state-only step: a step of a fused sequence before its last, for a full group, Philox
+// draws, no auto-reset. Nothing can read an inner step's reward, done or err, and the next state
+// needs neither the out-of-fuel flag (a dead ship keeps moving) nor which error was raised, only
+// whether one was. So there is no reward, no out-of-fuel compare, and the action's checks are one
+// bit. The state arithmetic, its order and every Philox counter are step_group_agent's.
+// Position, origin and dest live in Carried from step to step, one register per env, so
+// consecutive steps neither unpack nor pack bytes; fuel, cargo and the action are G's (of G the
+// step touches f, c and a only). The cell code under the ship is carried too (after a move
+// it is the byte the ground test read at the cell moved to), so a step makes one cell lookup per
+// env, with the table's LDS address riding in the dot product (lds_cell). The complements of the
+// action-range compares are s_not of their lane masks (with_complement). The caller draws FUEL
+// and GATE together (fb, gb: philox.h, draw2). The ranked LOSS draw is step_group_agent's, line
+// for line: as a shared helper it compiled to another instruction order in both steps.
+// The take and the arrival test run only for a wave that needs them (two ballots per step,
+// scalar branches). Ships are mostly at sea, so most wave-steps run neither
+// (profiles/seq_guard/freq.json).
+struct Carried {
+    uint32_t pos[4];  // x | y << 16
+    int org[4], dst[4];
+    uint32_t code[4];   // the cell code under the ship, w.cell[cell_of(pos)]
+    const int2* take;   // the block's stocks by cell code (stock_by_code), the same for every env
+};
+template <bool kNt>
+__device__ __forceinline__ void step_group_state(const LdsWorld& w, const Key& qk, uint32_t t, const U4& fb,
+                                                 const U4& gb, Group<false, false, kNt>& G, Carried& U) {
+    const int P = w.P;
+    const uint32_t lim = (uint32_t)(w.H - 1) | ((uint32_t)(w.W - 1) << 16);
+    const uint32_t wh = (uint32_t)w.W | (1u << 16);
+    const uint32_t pm1 = P > 0 ? (uint32_t)(P - 1) : 0u;  // clamp for table reads whose value an error discards
+    // The take guard. A take passes only for a ship on a port cell, so a wave none of whose
+    // envs has a take action on a non-water cell (code != 0: wider than "a port's code", so
+    // ground and codes past P only send their wave here) skips the whole take: the stock
+    // read, the amount checks, the cargo add and the fuel's f64 conversion. The vote is a
+    // ballot, so the branch is scalar; it reads this step's actions and the codes before
+    // the move. A passed take changes only cargo and fuel, and its env neither moves nor
+    // selects, so it is applied here and the step below runs without it: cargo is what the
+    // full step's `tc_ok ? cargo + amount : cargo` gives, and fuel reaches the fuel update as
+    // fuel + amount, to which that update adds -0.0, which changes no bit of any value.
+    bool take_any = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) take_any |= (G.a[j] >= 4 + P) & (U.code[j] != 0);
+    if (__builtin_amdgcn_ballot_w64(take_any) != 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int act = G.a[j];
+            const bool lt_tc = act < 54 + P;
+            const int amount = act - (lt_tc ? 4 + P : 54 + P);
+            // the stocks by the carried cell code, zero off a port: 0 < amount <= stock
+            // then holds at a port with the stock only (and never when P == 0)
+            const int2 st2 = U.take[U.code[j]];
+            const int stock = lt_tc ? st2.y : st2.x;
+            const bool ok_take = (act >= 4 + P) & (amount > 0) & (amount <= stock);
+            G.c[j] = (ok_take & lt_tc) ? G.c[j] + amount : G.c[j];
+            G.f[j] = (ok_take & !lt_tc) ? G.f[j] + (double)amount : G.f[j];
+        }
+    }
+    uint32_t pos[4];
+    int dst[4], cg[4];
+    bool do_move[4], moved[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        // [0,4) moves (-4..-1 wrap), [4, 4+P) SELECT; the takes are done
+        const int act = G.a[j];
+        const bool bad = act < -4;
+        const Pred2 mv = with_complement(act < 4), sel = with_complement(act < 4 + P);
+        const int val = act - 4;  // only a select reads it
+        const uint32_t dxy = w.moves[act & 3];
+        const uint32_t p = U.pos[j];
+        dst[j] = U.dst[j];
+        cg[j] = G.c[j];
+        // MOVE (_move_ship :273-339)
+        const uint32_t np = pk_add_u16(p, dxy);
+        const bool inb = pk_min_u16(np, lim) == np;  // _is_within_map (:284); -1 wraps to 0xffff
+        const bool nodest = dst[j] == SE_NONE;       // :276
+        const uint32_t cp = (!nodest & inb) ? np : p;  // in-range cell for the lookup
+        uint32_t code_cp = lds_cell(lds_address(w.cell), cp, wh);
+        // carried as a full register (as a byte it is masked again before every select)
+        asm("" : "+v"(code_cp));
+        const bool ground = code_cp == kCellGround;  // :293
+        // step_group_agent's error cascade as its one bit: no check of the action's own type
+        // failed (mask arithmetic, no ?: : a branch here would take the LDS lookups with it).
+        // A take is not among them: the take guard has applied it, and nothing below reads
+        // whether a take passed.
+        const bool same = U.org[j] == val;
+        const bool ok_mv = mv.t & !nodest & inb;
+        const bool ok_sel = mv.f & sel.t & !same;
+        const bool ok = !bad & (P != 0) & (ok_mv | ok_sel);
+        do_move[j] = ok & mv.t;
+        moved[j] = do_move[j] & !ground;
+        const bool sel_ok = ok & mv.f & sel.t;
+        pos[j] = moved[j] ? cp : p;
+        U.code[j] = moved[j] ? code_cp : U.code[j];  // the ground test's read
+        dst[j] = sel_ok ? val : dst[j];
+    }
+    uint32_t fire = 0, arrive = 0;
+    // The arrival guard. An arrival (:325) happens on a port's cell, and the world image
+    // stamps every port's cell with a non-zero code, so a wave none of whose movers is on
+    // a non-water cell after the move has no arrival and reads no destination position.
+    // The vote is a ballot (a scalar branch) over the codes as the move left them. The
+    // test itself stays the position compare: two ports may share a cell, and dest may
+    // hold anything a caller loaded. (A mover selects nothing, so dst is still its dest.)
+    bool arrive_any = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) arrive_any |= do_move[j] & (U.code[j] != 0);
+    if (__builtin_amdgcn_ballot_w64(arrive_any) != 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            arrive |= (uint32_t)(do_move[j] & (pos[j] == w.pos[min((uint32_t)dst[j], pm1)])) << j;
+    }
+    double f[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        // fuel cost (:103-104); a ship that does not move adds -0.0, which leaves every value as it is
+        const double scale = 1.0 + (-0.1 + (double)fb.v[j] * kFifthPerWord);
+        f[j] = G.f[j] + (moved[j] ? -scale : -0.0);
+        // the gate (:318-323), as step_group_agent tests it
+        const uint32_t thr = w.gate_thr[min(max(cg[j], 0), 50)];
+        const bool fires = do_move[j] & (cg[j] > 0) & (gb.v[j] <= thr);
+        fire |= (uint32_t)fires << j;
+    }
+    // the flags travel as opaque VGPR bit masks (no lane masks live in SGPR pairs
+    // across the draw blocks below)
+    asm volatile("" : "+v"(fire), "+v"(arrive));
+    int org[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        org[j] = U.org[j];
+        U.pos[j] = pos[j];
+        G.f[j] = f[j];
+    }
+    // cargo loss and arrival, only in waves with a firing gate / an arrival
+    if (fire) {
+        uint32_t lt[4], v1[4], v2[4], v3[4];
+        const uint32_t rk[4] = {0u, fire & 1u, (uint32_t)__popc(fire & 3u), (uint32_t)__popc(fire & 7u)};
+        U4 rr = draw(qk, t, loss_slot(0));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            lt[j] = rr.v[0];
+            v1[j] = rr.v[1];
+            v2[j] = rr.v[2];
+            v3[j] = rr.v[3];
+        }
+#pragma unroll
+        for (uint32_t q = 1; q < 4; ++q) {
+            if (__popc(fire) > q) {
+                rr = draw(qk, t, loss_slot(q));
+#pragma unroll
+                for (int j = (int)q; j < 4; ++j) {
+                    const bool take = rk[j] >= q;
+                    lt[j] = take ? rr.v[0] : lt[j];
+                    v1[j] = take ? rr.v[1] : v1[j];
+                    v2[j] = take ? rr.v[2] : v2[j];
+                    v3[j] = take ? rr.v[3] : v3[j];
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            // beta = the median of the three words * 2^-32 (the conversion is monotone)
+            const uint32_t lo = min(v1[j], v2[j]), hi = max(v1[j], v2[j]);
+            const uint32_t med = max(lo, min(hi, v3[j]));  // v_med3_u32
+            const int part = beta_part(med, cg[j]);
+            const int some = lt[j] > kTypeHi ? cg[j] : part;
+            const int loss = lt[j] < kTypeLo ? 0 : some;
+            const bool fj = (fire >> j) & 1u;
+            cg[j] = fj ? cg[j] - loss : cg[j];
+        }
+    }
+    if (arrive) {
+        const U4 ab = draw(qk, t, kSlotArrive);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool aj = (arrive >> j) & 1u;
+            const int nd = pick_other(ab.v[j], P, dst[j]);
+            cg[j] = aj ? 0 : cg[j];
+            org[j] = aj ? dst[j] : org[j];
+            dst[j] = aj ? nd : dst[j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        U.org[j] = org[j];
+        U.dst[j] = dst[j];
+        G.c[j] = cg[j];
+    }
+}
+
 // The stocks by cell code for the state-only steps' take checks: 256 (fuel, cargo) pairs,
 // port i's at code i + 1 and zeros at every other code (0 water, kCellGround, codes past P),
 // so `0 < amount <= stock` is false wherever the ship is on no port. One entry per thread of
@@ -1992,16 +2045,17 @@ __device__ __forceinline__ void stock_by_code(const LdsWorld& w, int2* take) {
 // launch, on step_kernel's grid and ownership. Nothing outside the stream can observe the
 // state between two steps of one sequence, and a step reads only x, y, origin, dest, cargo,
 // fuel and its action, so a group is loaded once, stepped `steps` times in registers
-// (step_group_agent<kKeep>: counter A.t + k, action row k at A.act + k * ld) and stored once,
-// with the last step's reward, done and err. Against a launch per step that leaves out, per
+// (counter A.t + k, action row k at A.act + k * ld) and stored once, with the last step's
+// reward, done and err. Against a launch per step that leaves out, per
 // step, the launch, the world staging, 32 B of state loads and 38 B of stores per env; what a
 // step still moves is its 4 B action. Row k + 1 is loaded before step k's arithmetic, so its
 // latency (rows are read once, from HBM) hides behind the step. iters > 1: the group loop is
 // the outer one.
 // Only the last step's reward, done and err exist anywhere, so steps 0 .. steps - 2 run the
-// state-only step (step_group_agent<kLean>), with x | y, origin and dest unpacked once before
-// them and packed once after, and step steps - 1 alone runs the full one. Every launch of a
-// split run therefore ends with a full step; steps == 1 is the full step by itself.
+// state-only step (step_group_state), with x | y, origin and dest unpacked once before them
+// and packed once after, and step steps - 1 alone runs the full one (step_group_agent<kKeep>).
+// Every launch of a split run therefore ends with a full step; steps == 1 is the full step by
+// itself.
 template <bool kNt>
 __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4))) void step_seq_kernel(
     StepArgs A, int32_t steps, int64_t ld) {
@@ -2047,7 +2101,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
             Carried U;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                U.pos[j] = __builtin_amdgcn_perm(G.y, G.x, (uint32_t)j | 0x0c000c00u | ((uint32_t)(4 + j) << 16));
+                U.pos[j] = unpack_pos(G.x, G.y, j);
                 U.org[j] = byte_of(G.org, j);
                 U.dst[j] = byte_of(G.dst, j);
                 U.code[j] = w.cell[cell_of(U.pos[j], (uint32_t)w.W | (1u << 16))];
@@ -2065,16 +2119,12 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                 int32_t nxt[4];
                 ld4_full<kNt>(row, g0, nxt);
                 const U4x2 fg = draw2(qk, inv, t);
-                const Draws D{fg.fuel, fg.gate, U4{{0u, 0u, 0u, 0u}}, U4{{0u, 0u, 0u, 0u}}};
-                step_group_agent<false, true, kNt, false, false, true, true>(A, w, G, at, bs, F, D, t, nullptr, &U);
+                step_group_state(w, qk, t, fg.fuel, fg.gate, G, U);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
             }
-            // back into the Group's packed bytes (step_group_agent's own packing)
-            const uint32_t t01 = __builtin_amdgcn_perm(U.pos[1], U.pos[0], 0x06020400u);  // x0 x1 y0 y1
-            const uint32_t t23 = __builtin_amdgcn_perm(U.pos[3], U.pos[2], 0x06020400u);  // x2 x3 y2 y3
-            G.x = __builtin_amdgcn_perm(t23, t01, 0x05040100u);
-            G.y = __builtin_amdgcn_perm(t23, t01, 0x07060302u);
+            // back into the Group's packed bytes
+            pack_pos(U.pos, G.x, G.y);
             G.org = G.dst = 0;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {

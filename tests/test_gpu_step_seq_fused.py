@@ -3,47 +3,14 @@ state stays in registers from step to step, stored once with the last step's out
 Every comparison here is exact: against K VecEnv.step calls on a twin env, against the C
 oracle, and against the unsplit run wherever the run is cut (the timer mark, the per-launch
 step cap, several groups per thread, the per-step baseline)."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
 from conftest import golden_water
+from step_seq_support import assert_same, environ, gpu_lib, snapshot  # noqa: F401
 
 torch = pytest.importorskip("torch")
-pytestmark = pytest.mark.gpu
-
-STATE = ("x", "y", "fuel", "cargo", "origin", "dest")
-OUTPUTS = ("reward", "done", "err")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from shippingenv_amd import build
-
-    build.build(verbose=False)
-
-
-@contextlib.contextmanager
-def environ(**kv):
-    """Set variables the library reads at se_create; put the old values back afterwards."""
-    old = {k: os.environ.get(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("gpu_lib")]
 
 
 def make_env(n, ports64=False, seed=22, auto=False, **env):
@@ -52,19 +19,6 @@ def make_env(n, ports64=False, seed=22, auto=False, **env):
     ports = random_water_ports(golden_water(), 64, seed=3) if ports64 else None
     with environ(**env):
         return VecEnv(n, seed=seed, ports=ports, auto_reset=auto)
-
-
-def snapshot(env):
-    """Every field a step writes, as host arrays (fuel as its bits)."""
-    torch.cuda.synchronize()
-    out = {f: getattr(env, f).cpu().numpy() for f in STATE + OUTPUTS}
-    out["fuel"] = out["fuel"].view(np.int64)
-    return out
-
-
-def assert_same(got, want, what):
-    for f in STATE + OUTPUTS:
-        np.testing.assert_array_equal(got[f], want[f], err_msg=f"{what}: {f}")
 
 
 def action_rows(env, rows, pad=8):
@@ -151,7 +105,7 @@ def test_fused_vs_oracle(oracle_mod):
         np.testing.assert_array_equal(got[f].astype(np.int32), getattr(st, f), err_msg=f)
     for f in ("origin", "dest"):
         np.testing.assert_array_equal(np.where(got[f] == 255, -1, got[f].astype(np.int32)), getattr(st, f), err_msg=f)
-    np.testing.assert_array_equal(got["fuel"], st.fuel.view(np.int64), err_msg="fuel bits")
+    np.testing.assert_array_equal(got["fuel"].view(np.int64), st.fuel.view(np.int64), err_msg="fuel bits")
     np.testing.assert_array_equal(got["reward"], st.reward.astype(np.float32), err_msg="reward")
     env.close()
 

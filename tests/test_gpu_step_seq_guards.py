@@ -28,26 +28,16 @@ whole and split, with and without non-temporal loads, and with several groups pe
 import numpy as np
 import pytest
 
-import test_gpu_step_seq_lean as lean
-from test_gpu_step_seq_lean import AMOUNT, NOT_AT_PORT, OK, TAIL, assert_same, device_rows, empty_state, snapshot
-from test_gpu_step_seq_trim import (E_, K_SCN, N_, N_GENERIC, S_, SHARED, SMALL, assert_generic_coverage, load, oracle_trace,
-                                    run_fused, ship)
+from step_seq_support import (AMOUNT, NOT_AT_PORT, OK, TAIL, assert_same, device_rows, empty_state, gpu_lib, load,  # noqa: F401
+                              oracle_trace, run_fused, snapshot, twin_trace)
+from test_gpu_step_seq_lean import world_of
+from test_gpu_step_seq_trim import E_, K_SCN, N_, N_GENERIC, S_, SHARED, SMALL, assert_generic_coverage, ship
 
-torch = pytest.importorskip("torch")
 gpu = pytest.mark.gpu
 
 WAVE = 256  # envs of one wave: 64 lanes, a group of 4 envs each
 ACTORS = (0, 3, 255, 256, 1023, 1024, 1028)
 INNER = range(K_SCN - 1)
-
-
-@pytest.fixture(scope="module")
-def gpu_lib():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from shippingenv_amd import build
-
-    build.build(verbose=False)
 
 
 def cell_codes(world):
@@ -186,7 +176,7 @@ def test_single_actor_fused_equals_step_calls(label, gpu_lib, oracle_mod):
     a, b = world.env(N_GENERIC), world.env(N_GENERIC)
     for actor in ACTORS:
         _, init, acts = actor_run(label, actor)
-        load(a, init, 0)
+        load(a, init)
         dev = device_rows(a, acts)
         trace = []
         for k in range(len(acts)):
@@ -195,7 +185,7 @@ def test_single_actor_fused_equals_step_calls(label, gpu_lib, oracle_mod):
         assert_actor_claims(label, actor, init, acts, trace)
         for k, want in enumerate(oracle_trace(oracle_mod, world, init, acts)):
             assert_same(trace[k], want, f"{label} at env {actor}: twin vs oracle, step {k}")
-        run_fused(b, init, device_rows(b, acts), trace, K_SCN, 0, None, f"{label} at env {actor}")
+        run_fused(b, init, device_rows(b, acts), trace, K_SCN, None, f"{label} at env {actor}")
     a.close()
     b.close()
 
@@ -209,7 +199,7 @@ def sparse_run(seed=SPARSE_SEED):
     """The 100 x 100 map with its 5 ports. About one env in 64 starts on a port and one in 64 on
     the cell before its destination; the rest are in open sea. Actions are drawn as
     test_gpu_step_seq_trim.generic_run draws them."""
-    world = lean.world_of(5)
+    world = world_of(5)
     n, rows = N_GENERIC, K_SPARSE + TAIL
     rng = np.random.default_rng(seed)
     st = empty_state(n)
@@ -248,7 +238,7 @@ def test_sparse_run_on_the_oracle(oracle_mod):
     world, init, acts = sparse_run()
     on_port = np.array([[int(init["x"][i]), int(init["y"][i])] in world.ports for i in range(N_GENERIC)])
     assert 1 / 128 < on_port.mean() < 1 / 32
-    assert_sparse_coverage(world, init, acts, lean.oracle_trace(oracle_mod, world, init, acts))
+    assert_sparse_coverage(world, init, acts, oracle_trace(oracle_mod, world, init, acts))
 
 
 _SPARSE = []
@@ -258,7 +248,7 @@ def sparse_reference():
     """The twin's 33 + TAIL recorded steps (read-only, shared by the cases)."""
     if not _SPARSE:
         world, init, acts = sparse_run()
-        _SPARSE.append((world, init, acts, lean.twin_trace(world, init, acts)))
+        _SPARSE.append((world, init, acts, twin_trace(world, init, acts)))
     return _SPARSE[0]
 
 
@@ -270,11 +260,11 @@ def test_sparse_run_fused_equals_step_calls(env, gpu_lib, oracle_mod):
     non-temporal loads, and with one workgroup (several groups per thread, a vote per group)."""
     world, init, acts, trace = sparse_reference()
     assert_sparse_coverage(world, init, acts, trace)
-    want = lean.oracle_trace(oracle_mod, world, init, acts)
+    want = oracle_trace(oracle_mod, world, init, acts)
     for k in (0, 1, K_SPARSE - 1, K_SPARSE + TAIL - 1):
         assert_same(trace[k], want[k], f"sparse: twin vs oracle, step {k}")
     b = world.env(N_GENERIC, **env)
     dev = device_rows(b, acts)
     for K in (2, K_SPARSE):
-        lean.run_fused(b, init, dev, trace, K, None, f"sparse K={K} {env}")
+        run_fused(b, init, dev, trace, K, None, f"sparse {env}")
     b.close()

@@ -1,6 +1,6 @@
 """The fused se_step_seq runs every step but a launch's last in a state-only mode
-(step_group_agent<kLean>: no reward, no done, no err, the action's checks as one bit, x | y,
-origin and dest carried unpacked) and only the last step in full. What could go wrong is the
+(step_group_state: no reward, no done, no err, the action's checks as one bit, x | y, origin
+and dest carried unpacked) and only the last step in full. What could go wrong is the
 state an inner step leaves behind and whose outputs a run stores, so every scenario here is
 stepped by a twin env through K VecEnv.step calls (recorded step by step), then by one
 step_seq call, and compared exactly, fuel by its bits; 2 plain steps on both follow, so a wrong
@@ -15,52 +15,18 @@ what they say on a machine without a GPU.
 An agent index past the action space is no SE_ERR_BAD_INDEX in this project (nor in the
 reference, whose decode only raises below -4): it decodes as TAKE_FUEL of an amount above every
 stock, so it raises SE_ERR_AMOUNT at a port and SE_ERR_NOT_AT_PORT at sea. Both are covered."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
 from conftest import golden_water
+from step_seq_support import (AMOUNT, BAD_INDEX, NO_DEST, NO_PORTS, NONE, NOT_AT_PORT, OK, OOB, SAME_PORT, STATE, TAIL,  # noqa: F401
+                              assert_same, device_rows, empty_state, environ, gpu_lib, oracle_trace, run_fused,
+                              steps_before_last, twin_trace)
 
-torch = pytest.importorskip("torch")
 gpu = pytest.mark.gpu
 
 SEED = 22
-STATE = ("x", "y", "fuel", "cargo", "origin", "dest")
-OUTPUTS = ("reward", "done", "err")
-NONE = 255
-OK, OOB, SAME_PORT, NOT_AT_PORT, AMOUNT, NO_DEST, NO_PORTS, BAD_INDEX = 0, 1, 2, 4, 5, 6, 8, 9
 MOVES = ((0, -1), (-1, 0), (0, 1), (1, 0))  # N, E, S, W as (dx, dy)
-TAIL = 2  # plain steps after the fused run
-
-
-@pytest.fixture(scope="module")
-def gpu_lib():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from shippingenv_amd import build
-
-    build.build(verbose=False)
-
-
-@contextlib.contextmanager
-def environ(**kv):
-    """Set variables the library reads at se_create; put the old values back afterwards."""
-    old = {k: os.environ.get(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 class World:
@@ -102,12 +68,12 @@ class World:
         self.edge = ([(0, y, 1) for y in range(0, self.W, 7)] + [(self.H - 1, y, 3) for y in range(0, self.W, 7)]
                      + [(x, 0, 0) for x in range(0, self.H, 7)] + [(x, self.W - 1, 2) for x in range(0, self.H, 7)])
 
-    def env(self, n, **env):
+    def env(self, n, seed=SEED, env_id_base=0, **env):
         from shippingenv_amd.vec import VecEnv
 
         with environ(**env):
             return VecEnv(n, water=self.water, ports=self.ports, port_fuel=self.fuel_stock,
-                          port_cargo=self.cargo_stock, seed=SEED)
+                          port_cargo=self.cargo_stock, seed=seed, env_id_base=env_id_base)
 
     def oracle(self, O):
         px = [p[0] for p in self.ports]
@@ -124,79 +90,7 @@ def world_of(n_ports):
     return _WORLDS[n_ports]
 
 
-# ----------------------------------------------------------------- states, steppers, traces
-def empty_state(n):
-    return {"x": np.zeros(n, np.int32), "y": np.zeros(n, np.int32), "fuel": np.zeros(n, np.float64),
-            "cargo": np.zeros(n, np.int32), "origin": np.full(n, NONE, np.int32), "dest": np.full(n, NONE, np.int32)}
-
-
-def load(env, st):
-    """Write the env's tensors and put its step counter at 0."""
-    for f, dt in (("x", np.uint8), ("y", np.uint8), ("fuel", np.float64), ("cargo", np.int32),
-                  ("origin", np.uint8), ("dest", np.uint8)):
-        getattr(env, f).copy_(torch.from_numpy(st[f].astype(dt)))
-    env.reward.zero_()
-    env.done.zero_()
-    env.err.zero_()
-    env.set_counters(0, 0)
-
-
-def snapshot(env):
-    """Every field a step writes, as host arrays: integers as int32, fuel f64, reward f32."""
-    torch.cuda.synchronize()
-    out = {f: getattr(env, f).cpu().numpy() for f in STATE + OUTPUTS}
-    return {f: (v if f in ("fuel", "reward") else v.astype(np.int32)) for f, v in out.items()}
-
-
-def assert_same(got, want, what):
-    for f in STATE + OUTPUTS:
-        g, w = (got[f].view(np.int64), want[f].view(np.int64)) if f == "fuel" else (got[f], want[f])
-        np.testing.assert_array_equal(g, w, err_msg=f"{what}: {f}")
-
-
-def device_rows(env, acts):
-    """[rows, n] device view of the host rows at a padded stride ld > n (a multiple of 4)."""
-    rows, n = acts.shape
-    ld = ((n + 3) & ~3) + 8
-    buf = torch.full((rows, ld), -99, dtype=torch.int32, device=env.device)  # padding: a bad index if ever read
-    buf[:, :n].copy_(torch.from_numpy(acts))
-    return buf[:, :n]
-
-
-def twin_trace(world, init, acts):
-    """trace[k]: the snapshot after step k of len(acts) VecEnv.step calls from init."""
-    env = world.env(len(init["x"]))
-    load(env, init)
-    dev = device_rows(env, acts)
-    trace = []
-    for k in range(len(acts)):
-        env.step(dev[k].contiguous())
-        trace.append(snapshot(env))
-    env.close()
-    for s in trace:
-        for v in s.values():
-            v.setflags(write=False)
-    return trace
-
-
-def oracle_trace(O, world, init, acts):
-    """The same trace from the C oracle's stepper (origin / dest None is -1 there)."""
-    n = len(init["x"])
-    w = world.oracle(O)
-    st = O.OracleState(n)
-    for f in STATE:
-        getattr(st, f)[:] = np.where(init[f] == NONE, -1, init[f]) if f in ("origin", "dest") else init[f]
-    trace = []
-    for k in range(len(acts)):
-        O.step(w, st, actions=np.ascontiguousarray(acts[k]), seed=SEED, t=k)
-        s = {f: getattr(st, f).copy() for f in STATE + ("done", "err")}
-        for f in ("origin", "dest"):
-            s[f] = np.where(s[f] < 0, NONE, s[f]).astype(np.int32)
-        s["reward"] = st.reward.astype(np.float32)
-        trace.append(s)
-    return trace
-
-
+# ----------------------------------------------------------------- the fused run
 def fused_matches_twin(world, init, acts, trace, K, mark_after=None, nt="1", **env):
     """One step_seq of rows 0 .. K-1 from init equals the twin after K steps, and after TAIL
     plain steps more."""
@@ -204,27 +98,6 @@ def fused_matches_twin(world, init, acts, trace, K, mark_after=None, nt="1", **e
     dev = device_rows(b, acts)
     run_fused(b, init, dev, trace, K, mark_after, f"K={K} nt={nt} {env}")
     b.close()
-
-
-def run_fused(b, init, dev, trace, K, mark_after, what):
-    load(b, init)
-    if mark_after is None:
-        r, d, e = b.step_seq(dev[:K])
-    else:
-        ev = torch.cuda.Event(enable_timing=True)
-        r, d, e = b.step_seq(dev[:K], mark=ev, mark_after=mark_after)
-    assert r.data_ptr() == b.reward.data_ptr() and d.data_ptr() == b.done.data_ptr() and e.data_ptr() == b.err.data_ptr()
-    assert_same(snapshot(b), trace[K - 1], f"{what} mark_after={mark_after}: after the fused run")
-    assert b.counters[0] == K
-    for k in range(K, K + TAIL):
-        b.step(dev[k].contiguous())
-    assert_same(snapshot(b), trace[K + TAIL - 1], f"{what} mark_after={mark_after}: {TAIL} plain steps later")
-
-
-def steps_before_last(init, acts, trace, K):
-    """(k, before, action row, after) of the inner steps k < K - 1."""
-    for k in range(K - 1):
-        yield k, (init if k == 0 else trace[k - 1]), acts[k], trace[k]
 
 
 # ----------------------------------------------------------------- scenarios

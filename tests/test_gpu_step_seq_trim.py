@@ -15,23 +15,13 @@ and the tests without the gpu mark assert the same claims on the C oracle."""
 import numpy as np
 import pytest
 
-from test_gpu_step_seq_lean import (AMOUNT, NO_DEST, NO_PORTS, NONE, NOT_AT_PORT, OK, OOB, STATE, TAIL, assert_same,
-                                    device_rows, empty_state, environ, snapshot)
+from step_seq_support import (AMOUNT, NO_DEST, NO_PORTS, NONE, NOT_AT_PORT, OK, OOB, TAIL, assert_same, device_rows,  # noqa: F401
+                              empty_state, environ, gpu_lib, oracle_trace, run_fused, twin_trace)
 
-torch = pytest.importorskip("torch")
 gpu = pytest.mark.gpu
 
 N_, E_, S_, W_ = 0, 1, 2, 3  # moves by (dx, dy): (0, -1), (-1, 0), (0, 1), (1, 0); x is the map row
 K_SCN = 4  # rows 0 .. 2 run as state-only steps, row 3 in full
-
-
-@pytest.fixture(scope="module")
-def gpu_lib():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from shippingenv_amd import build
-
-    build.build(verbose=False)
 
 
 class World:
@@ -225,62 +215,6 @@ def assert_claims(name, which, trace):
                 assert (trace[k][field][envs] == want).all(), f"{label}: step {k} {field} {trace[k][field][envs][0]} != {want}"
 
 
-# ----------------------------------------------------------------- steppers
-def load(env, st, t0):
-    for f, dt in (("x", np.uint8), ("y", np.uint8), ("fuel", np.float64), ("cargo", np.int32),
-                  ("origin", np.uint8), ("dest", np.uint8)):
-        getattr(env, f).copy_(torch.from_numpy(st[f].astype(dt)))
-    env.reward.zero_()
-    env.done.zero_()
-    env.err.zero_()
-    env.set_counters(t0, 0)
-
-
-def twin_trace(world, init, acts, seed=22, env_id_base=0, t0=0):
-    env = world.env(len(init["x"]), seed=seed, env_id_base=env_id_base)
-    load(env, init, t0)
-    dev = device_rows(env, acts)
-    trace = []
-    for k in range(len(acts)):
-        env.step(dev[k].contiguous())
-        trace.append(snapshot(env))
-    env.close()
-    for s in trace:
-        for v in s.values():
-            v.setflags(write=False)
-    return trace
-
-
-def oracle_trace(O, world, init, acts, seed=22, env_id_base=0, t0=0):
-    n = len(init["x"])
-    w = world.oracle(O)
-    st = O.OracleState(n)
-    for f in STATE:
-        getattr(st, f)[:] = np.where(init[f] == NONE, -1, init[f]) if f in ("origin", "dest") else init[f]
-    trace = []
-    for k in range(len(acts)):
-        O.step(w, st, actions=np.ascontiguousarray(acts[k]), seed=seed, env_id_base=env_id_base, t=(t0 + k) & 0xffffffff)
-        s = {f: getattr(st, f).copy() for f in STATE + ("done", "err")}
-        for f in ("origin", "dest"):
-            s[f] = np.where(s[f] < 0, NONE, s[f]).astype(np.int32)
-        s["reward"] = st.reward.astype(np.float32)
-        trace.append(s)
-    return trace
-
-
-def run_fused(b, init, dev, trace, K, t0, mark_after, what):
-    load(b, init, t0)
-    if mark_after is None:
-        b.step_seq(dev[:K])
-    else:
-        b.step_seq(dev[:K], mark=torch.cuda.Event(enable_timing=True), mark_after=mark_after)
-    assert_same(snapshot(b), trace[K - 1], f"{what} K={K} mark_after={mark_after}: after the fused run")
-    assert b.counters[0] == t0 + K
-    for k in range(K, K + TAIL):
-        b.step(dev[k].contiguous())
-    assert_same(snapshot(b), trace[K + TAIL - 1], f"{what} K={K} mark_after={mark_after}: {TAIL} plain steps later")
-
-
 # ----------------------------------------------------------------- the hand-built scenarios
 SCN_WORLDS = ("small", "shared", "one", "none", "many")
 
@@ -312,7 +246,7 @@ def test_scenario_fused_equals_step_calls(name, nt, gpu_lib, oracle_mod):
         assert_same(trace[k], want, f"{name}: twin vs oracle, step {k}")
     for env in ({}, {"SHIPENV_SEQ_MAX_STEPS": "3"}):
         b = world.env(len(init["x"]), SHIPENV_NT_LOADS=nt, **env)
-        run_fused(b, init, device_rows(b, acts), trace, K_SCN, 0, None, f"{name} nt={nt} {env}")
+        run_fused(b, init, device_rows(b, acts), trace, K_SCN, None, f"{name} nt={nt} {env}")
         b.close()
 
 
@@ -398,7 +332,7 @@ def test_draws_and_peel_edges(draws, nt, gpu_lib, oracle_mod):
     dev = device_rows(b, acts)
     for K in KS:
         for mark_after in [None] + sorted({1, K - 1} & set(range(1, K))):
-            run_fused(b, init, dev, trace, K, t0, mark_after, f"{draws} nt={nt}")
+            run_fused(b, init, dev, trace, K, mark_after, f"{draws} nt={nt}", t0)
     b.close()
 
 
@@ -411,5 +345,5 @@ def test_one_workgroup_walks_several_groups(gpu_lib):
     b = GENERIC.env(N_GENERIC, seed=seed, env_id_base=base, SHIPENV_STEP_BLOCKS="1")
     dev = device_rows(b, acts)
     for K in (2, 33):
-        run_fused(b, init, dev, trace, K, t0, None, "one workgroup")
+        run_fused(b, init, dev, trace, K, None, "one workgroup", t0)
     b.close()
