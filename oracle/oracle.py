@@ -52,6 +52,7 @@ def _lib():
     lib.orc_feistel_perm.restype = u32
     lib.orc_replay_pick.argtypes = [i64, i64, P, u64, u32, P]
     lib.orc_rollout.argtypes = [P, i64] + [P] * 6 + [i64, P, i32, i32, u64, i64, P, P, P]
+    lib.orc_rollout_trace.argtypes = lib.orc_rollout.argtypes + [P]
     return lib
 
 
@@ -211,16 +212,32 @@ def sample_actions(world, st, *, seed, env_id_base=0, t=0):
     return ty, a, b
 
 
-def rollout(world, st, src, *, max_steps, max_attempts, seed, rollout_base=0):
-    """MCTS random rollouts (agents/mcts.py:211-238) -> (ret f64, steps i32, status i32)."""
+class RolloutLog(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in (
+        "used", "raised", "beta_cargo", "x", "y", "fuel", "cargo", "origin", "dest")]
+
+
+def rollout(world, st, src, *, max_steps, max_attempts, seed, rollout_base=0, trace=False):
+    """MCTS random rollouts (agents/mcts.py:211-238) -> (ret f64, steps i32, status i32).
+
+    trace=True appends a dict of per-rollout arrays (orc_rollout_trace): `used`, the OR of the
+    SE_USED_* bits over the counted steps; `raised`, the attempts whose step raised;
+    `beta_cargo`, the largest cargo a partial loss was taken from; and the ship when the
+    rollout ended (x, y, fuel, cargo, origin, dest; -1 = None)."""
     s = np.ascontiguousarray(src, np.int32)
     m = len(s)
     ret = np.zeros(m, np.float64)
     steps = np.zeros(m, np.int32)
     status = np.zeros(m, np.int32)
-    lib().orc_rollout(world.ref, st.n, *st.fields(), m, _p(s), max_steps, max_attempts, seed,
-                      rollout_base, _p(ret), _p(steps), _p(status))
-    return ret, steps, status
+    if not trace:
+        lib().orc_rollout(world.ref, st.n, *st.fields(), m, _p(s), max_steps, max_attempts, seed,
+                          rollout_base, _p(ret), _p(steps), _p(status))
+        return ret, steps, status
+    log = {f: np.zeros(m, np.float64 if f == "fuel" else np.int32) for f, _ in RolloutLog._fields_}
+    c_log = RolloutLog(*[_p(log[f]) for f, _ in RolloutLog._fields_])
+    lib().orc_rollout_trace(world.ref, st.n, *st.fields(), m, _p(s), max_steps, max_attempts, seed,
+                            rollout_base, _p(ret), _p(steps), _p(status), C.byref(c_log))
+    return ret, steps, status, log
 
 
 def feistel_perm(p, D, key):

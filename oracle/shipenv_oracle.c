@@ -530,8 +530,24 @@ int orc_rollout(const orc_world* w, int64_t n, const int32_t* x, const int32_t* 
                 const int32_t* dest, int64_t m, const int32_t* src, int32_t max_steps,
                 int32_t max_attempts, uint64_t seed, int64_t rollout_base, double* ret,
                 int32_t* steps, int32_t* status) {
+    return orc_rollout_trace(w, n, x, y, fuel, cargo, origin, dest, m, src, max_steps, max_attempts,
+                             seed, rollout_base, ret, steps, status, NULL);
+}
+
+/* orc_rollout, reporting per rollout what it went through (tr may be NULL; a bad source
+ * leaves zeros and final fields of -1) */
+int orc_rollout_trace(const orc_world* w, int64_t n, const int32_t* x, const int32_t* y,
+                      const double* fuel, const int32_t* cargo, const int32_t* origin,
+                      const int32_t* dest, int64_t m, const int32_t* src, int32_t max_steps,
+                      int32_t max_attempts, uint64_t seed, int64_t rollout_base, double* ret,
+                      int32_t* steps, int32_t* status, const orc_rollout_log* tr) {
     for (int64_t r = 0; r < m; ++r) {
         const int64_t i = src[r];
+        if (tr) {
+            tr->used[r] = tr->raised[r] = tr->beta_cargo[r] = 0;
+            tr->x[r] = tr->y[r] = tr->cargo[r] = tr->origin[r] = tr->dest[r] = -1;
+            tr->fuel[r] = 0.0;
+        }
         if (i < 0 || i >= n) {
             ret[r] = 0.0;
             steps[r] = 0;
@@ -542,6 +558,7 @@ int orc_rollout(const orc_world* w, int64_t n, const int32_t* x, const int32_t* 
         load(&s, i, x, y, fuel, cargo, origin, dest);
         double total = 0.0;
         int32_t counted = 0, st = ROLL_ATTEMPTS;
+        int32_t used = 0, raised = 0, beta_cargo = 0;
         for (int32_t k = 0; k < max_attempts; ++k) {
             if (counted >= max_steps) { /* while not done and steps < max_rollout_steps (:225) */
                 st = ROLL_MAX_STEPS;
@@ -558,7 +575,13 @@ int orc_rollout(const orc_world* w, int64_t n, const int32_t* x, const int32_t* 
             source src = {NULL, seed, rollout_base + r, (uint32_t)k, 0, 0, blk, 0, 0};
             double rw = 0.0;
             int32_t d = 0;
-            if (step_typed(w, &s, ty, a, b, &src, &rw, &d) != E_OK) continue;
+            const int32_t had = s.cargo;
+            if (step_typed(w, &s, ty, a, b, &src, &rw, &d) != E_OK) {
+                raised += 1;
+                continue;
+            }
+            used |= src.used;
+            if ((src.used & U_BETA) && had > beta_cargo) beta_cargo = had;
             total += rw; /* total_reward += reward (:229) */
             counted += 1;
             if (d) {
@@ -570,6 +593,12 @@ int orc_rollout(const orc_world* w, int64_t n, const int32_t* x, const int32_t* 
         ret[r] = total;
         steps[r] = counted;
         status[r] = st;
+        if (tr) {
+            tr->used[r] = used;
+            tr->raised[r] = raised;
+            tr->beta_cargo[r] = beta_cargo;
+            store(&s, r, tr->x, tr->y, tr->fuel, tr->cargo, tr->origin, tr->dest);
+        }
     }
     return 0;
 }

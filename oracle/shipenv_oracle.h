@@ -96,6 +96,28 @@ int orc_rollout(const orc_world* w, int64_t n, const int32_t* x, const int32_t* 
                 int32_t max_attempts, uint64_t seed, int64_t rollout_base, double* ret,
                 int32_t* steps, int32_t* status);
 
+/* orc_rollout that also reports, per rollout, what it went through (tests use it to show
+ * that a scenario holds the event it is named after): used, the OR of the SE_USED_* bits
+ * over the counted steps; raised, the attempts whose step raised (retried, not counted);
+ * beta_cargo, the largest cargo a partial loss was taken from (0: none); and the ship
+ * when the rollout ended. ret, steps and status are orc_rollout's. */
+typedef struct {
+    int32_t* used;
+    int32_t* raised;
+    int32_t* beta_cargo;
+    int32_t* x;
+    int32_t* y;
+    double* fuel;
+    int32_t* cargo;
+    int32_t* origin;
+    int32_t* dest;
+} orc_rollout_log;
+int orc_rollout_trace(const orc_world* w, int64_t n, const int32_t* x, const int32_t* y,
+                      const double* fuel, const int32_t* cargo, const int32_t* origin,
+                      const int32_t* dest, int64_t m, const int32_t* src, int32_t max_steps,
+                      int32_t max_attempts, uint64_t seed, int64_t rollout_base, double* ret,
+                      int32_t* steps, int32_t* status, const orc_rollout_log* tr);
+
 void orc_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
 /* synthetic action stream used by the bench (config 3/4 mix), oracle side. */

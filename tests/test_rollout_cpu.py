@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import rollout_support as RS
 from conftest import GOLDEN, golden_water
 
 O = pytest.importorskip("oracle.oracle")
@@ -104,3 +105,67 @@ def test_rollout_zero_budgets():
     assert (status == 1).all() and (steps == 0).all() and (ret == 0).all()
     ret, steps, status = O.rollout(world, st, src, max_steps=10, max_attempts=0, seed=1)
     assert (status == 3).all() and (steps == 0).all()
+
+
+# ----------------------------------------------------------------- the rollout trace and the scenario tables
+
+def test_traced_rollout_equals_untraced():
+    """orc_rollout_trace returns orc_rollout's ret, steps and status, and its log is consistent
+    with them: a bad source logs nothing, a rollout that raised nothing and counted nothing ends
+    in the state it began in."""
+    _, world, st = fixture_world_state()
+    n = st.n
+    src = np.concatenate([np.arange(n), [-1, n, n + 7], np.arange(n)[::-1]]).astype(np.int32)
+    for ms, ma, base in ((60, 480, 0), (3, 4, (1 << 40) + 3), (0, 5, 9), (5, 0, 9)):
+        plain = O.rollout(world, st, src, max_steps=ms, max_attempts=ma, seed=3, rollout_base=base)
+        ret, steps, status, log = O.rollout(world, st, src, max_steps=ms, max_attempts=ma, seed=3,
+                                            rollout_base=base, trace=True)
+        np.testing.assert_array_equal(ret.view(np.uint64), plain[0].view(np.uint64))
+        np.testing.assert_array_equal(steps, plain[1])
+        np.testing.assert_array_equal(status, plain[2])
+        bad = status == RS.BAD_SRC
+        assert bad.sum() == 3
+        assert (log["x"][bad] == -1).all() and (log["used"][bad] == 0).all() and (log["raised"][bad] == 0).all()
+        assert (log["raised"] + steps <= ma).all() and (log["raised"] >= 0).all()
+        still = ~bad & (steps == 0)
+        for f in ("x", "y", "fuel", "cargo", "origin", "dest"):
+            np.testing.assert_array_equal(log[f][still], getattr(st, f)[src[still]], err_msg=f)
+        assert (log["used"][steps == 0] == 0).all()
+        # a partial loss is a BETA draw from the cargo it reports
+        assert ((log["beta_cargo"] > 0) == ((log["used"] & RS.USED_BETA) != 0)).all()
+    # the source state is not modified
+    _, _, st2 = fixture_world_state()
+    for f in ("x", "y", "fuel", "cargo", "origin", "dest"):
+        np.testing.assert_array_equal(getattr(st, f), getattr(st2, f))
+
+
+def test_scenario_worlds_are_what_the_actors_need():
+    assert RS.ONE.P == 1 and RS.MANY.P == 64 and len({tuple(p) for p in RS.MANY.ports}) == 64
+    assert RS.SHARED.ports[0] == RS.SHARED.ports[1] and RS.SHARED.cargo_stock[0] != RS.SHARED.cargo_stock[1]
+    assert RS.OPEN.cargo_stock[3] == 0 and RS.HEAVY.cargo_stock[0] == 1 << 23
+    big = RS.max_world()
+    assert big.P == 254 and (big.H, big.W) == (256, 256) and len({tuple(p) for p in big.ports}) == 240
+    for name, w in RS.WORLDS.items():
+        assert all(0 <= x < w.H and 0 <= y < w.W for x, y in w.ports), name
+        for label, sh, _ in RS.actors(name):
+            x, y = sh["cell"]
+            assert 0 <= x < w.H and 0 <= y < w.W and sh["cargo"] <= 1 << 28, label
+            assert sh["origin"] < w.P and sh["dest"] < w.P, label
+
+
+def test_scenarios_hold_what_they_claim_on_the_oracle():
+    """Every actor's 64 rollouts contain the event it is named after, and the tables together
+    go through all five statuses, the loss-type, beta and arrival draws, a retried step and a
+    partial loss from cargo >= 2^21. Conditions on the inputs, decided by the oracle alone."""
+    statuses, used, beta_cargo, raised = set(), 0, 0, 0
+    for name in RS.WORLDS:
+        s, u, b, r = RS.assert_claims(O, name)
+        statuses |= s
+        used |= u
+        beta_cargo, raised = max(beta_cargo, b), max(raised, r)
+    # BAD_SRC is a property of src, not of an actor
+    w, st = RS.OPEN.oracle(O), RS.table(O, "open")
+    statuses |= set(O.rollout(w, st, np.array([-1, st.n], np.int32), max_steps=1, max_attempts=1, seed=RS.SEED)[2].tolist())
+    assert statuses == {RS.DONE, RS.MAX_STEPS, RS.RAISED, RS.ATTEMPTS, RS.BAD_SRC}
+    assert used & RS.USED_LOSS_TYPE and used & RS.USED_BETA and used & RS.USED_ARRIVE
+    assert raised > 0 and beta_cargo >= RS.BIG
