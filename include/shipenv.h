@@ -307,6 +307,47 @@ int se_sample_actions(se_env* env, int32_t* type, int32_t* a, int32_t* b, uint32
 int se_rollout(se_env* env, const int32_t* src, int64_t m, int32_t max_steps, int32_t max_attempts,
                int64_t rollout_base, double* ret, int32_t* steps, int32_t* status, void* stream);
 
+/* One MCTS decision per env (agents/mcts.py:240-292, MCTSAgent.choose_action): `simulations`
+ * sequential simulations (UCB1 selection with c_param, one expansion, a random rollout of at
+ * most max_rollout_steps counted steps, backpropagation) on a private copy of the env, whose
+ * state is not modified, then best_child(c_param=0) over the root's children, or
+ * sample_action() when the root has none. Outputs (device, n entries, 16-byte aligned): the
+ * chosen typed action (type, a, b: se_step_typed's input) and status = SE_MCTS_*. tree and
+ * tree_count (both or neither; NULL: not wanted) receive every node of env i in creation
+ * order at tree[i * (simulations + 1) + j], j < tree_count[i], node 0 the root (parent -1,
+ * no action); entries from tree_count[i] on are not written.
+ * Draws: simulation s of env i uses Philox(seed, id), id = mcts_base + (env_id_base + i) *
+ * simulations + s (a per-rollout key like se_rollout's). Tree step d of the simulation (the
+ * selection steps, then the expansion step, d from 0) reads (d, slot 18): word 0 picks among
+ * the untried actions (the expansion step alone reads it), words 1-3 are u_fuel, u_gate,
+ * u_type; and, for a partial loss or an arrival, (d, slot 19): three beta uniforms, the new
+ * destination. The simulation's rollout draws what se_rollout draws for rollout_base + r = id.
+ * The root fallback reads word 0 of (0xFFFFFFFF, slot 18) of simulation 0's key.
+ * np.log(parent.visits) is read from a table the library fills with the host's log(). */
+#define SE_MCTS_OK 0             /* the chosen action */
+#define SE_MCTS_CUT 1            /* some rollout stopped at max_attempts (the reference keeps
+                                    retrying); the search went on with its partial return */
+#define SE_MCTS_RAISED 2         /* choose_action raises: argmax over no children at a fully
+                                    expanded node without possible actions, or sample_action
+                                    raising in _rollout or in the root fallback; the search
+                                    ends there; type = SE_SAMPLE_RAISES */
+#define SE_MCTS_NEVER_RETURNS 3  /* that sample_action never returns; type = SE_SAMPLE_NO_OTHER_PORT */
+typedef struct se_mcts_node {
+    int32_t parent;       /* index of the parent node, -1 at the root */
+    int32_t type, a, b;   /* the action that led here (0, 0, 0 at the root) */
+    int32_t visits;
+    int32_t reserved;     /* 0 */
+    double total_reward;
+} se_mcts_node;
+typedef struct se_mcts se_mcts;
+/* max_simulations in 1..256; the handle owns the tree scratch ((max_simulations + 1) * n nodes
+ * of 24 bytes). Destroy it before its env. */
+int se_mcts_create(se_mcts** out, se_env* env, int32_t max_simulations);
+int se_mcts_choose(se_mcts* m, int32_t simulations, double c_param, int32_t max_rollout_steps,
+                   int32_t max_attempts, int64_t mcts_base, int32_t* type, int32_t* a, int32_t* b,
+                   int32_t* status, se_mcts_node* tree, int32_t* tree_count, void* stream);
+int se_mcts_destroy(se_mcts* m);
+
 /* DQN policy step fused on the GPU (agents/dqn.py): DQNNetwork 6+4P -> 128 -> 128 -> A
  * (A = 4+P+250, :21-33) evaluated with bf16 MFMA and f32 accumulation on the
  * observation preprocess_state builds (utils/preprocessing.py:25-62; its constant port

@@ -11,8 +11,18 @@ reset) as gfx950 HIP kernels behind a C-ABI (include/shipenv.h):
   ``utils.preprocessing`` row layout and DQN validity, batched;
 * ``shippingenv_amd.policy`` / ``shippingenv_amd.dqn`` — the fused DQN policy and
   the vectorised DQN training loop;
+* ``shippingenv_amd.mcts.VecMCTSAgent`` (also ``shippingenv_amd.VecMCTSAgent``) — the
+  reference's MCTS planner, one decision per env and launch;
 * ``shippingenv_amd.maps`` — the map loader (``_initialize_map``);
 * ``shippingenv_amd.dist`` — one process per GPU, env sharding, RCCL stats.
 """
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):  # resolved on first use: importing the package stays free of torch
+    if name == "VecMCTSAgent":
+        from .mcts import VecMCTSAgent
+
+        return VecMCTSAgent
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -28,6 +28,9 @@ USED_FUEL_GATE, USED_LOSS_TYPE, USED_BETA, USED_ARRIVE, USED_MOVED = 1, 2, 4, 8,
 # se_sample_actions special types, se_rollout statuses
 SAMPLE_RAISES, SAMPLE_NO_OTHER_PORT = -1, -2
 ROLL_DONE, ROLL_MAX_STEPS, ROLL_RAISED, ROLL_ATTEMPTS, ROLL_BAD_SRC = 0, 1, 2, 3, 4
+# se_mcts_choose statuses
+MCTS_OK, MCTS_CUT, MCTS_RAISED, MCTS_NEVER_RETURNS = 0, 1, 2, 3
+MCTS_MAX_SIMULATIONS = 256
 
 # se_server_call ops
 SERVER_STEP, SERVER_RESET_TO = 1, 2
@@ -36,7 +39,7 @@ SERVER_STEP, SERVER_RESET_TO = 1, 2
 EXPORTS = (
     "se_create", "se_set_ports", "se_bind", "se_reset", "se_reset_to", "se_step", "se_step_seq", "se_step_seq_mark",
     "se_step_typed", "se_step_replay", "se_step_agent_replay", "se_observe", "se_valid_mask", "se_gen_actions",
-    "se_sample_actions", "se_rollout", "se_qnet_create", "se_qnet_set_weights", "se_policy", "se_policy_f32",
+    "se_sample_actions", "se_rollout", "se_mcts_create", "se_mcts_choose", "se_mcts_destroy", "se_qnet_create", "se_qnet_set_weights", "se_policy", "se_policy_f32",
     "se_qnet_repack", "se_policy_record", "se_policy_record_f32",
     "se_qnet_destroy", "se_replay_create", "se_replay_begin", "se_replay_end", "se_replay_end_reset", "se_step_record",
     "se_replay_size",
@@ -93,6 +96,9 @@ def _declare(lib):
         "se_gen_actions": [P, P, u32, P],
         "se_sample_actions": [P, P, P, P, u32, P],
         "se_rollout": [P, P, i64, i32, i32, i64, P, P, P, P],
+        "se_mcts_create": [C.POINTER(P), P, i32],
+        "se_mcts_choose": [P, i32, C.c_double, i32, i32, i64, P, P, P, P, P, P, P],
+        "se_mcts_destroy": [P],
         "se_qnet_create": [C.POINTER(P), P],
         "se_qnet_set_weights": [P, P, P, P, P, P, P, P],
         "se_policy": [P, P, C.c_double, u32, P, i64, P],

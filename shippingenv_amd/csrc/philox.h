@@ -37,6 +37,8 @@ enum Slot : uint32_t {
     kSlotReplay = 15,        // se_replay_sample, key (seed, 2^64 - 1), t = update: Feistel round keys
     kSlotReset2 = 16,
     kSlotReset3 = 17,
+    kSlotMcts = 18,          // MCTS tree step d, per simulation: untried-action choice, u_fuel, u_gate, u_type
+    kSlotMctsB = 19,         // MCTS tree step d (partial loss / arrival): 3 beta uniforms, dest
 };
 
 // RESET_r slot of the r-th auto-reset env of a quad

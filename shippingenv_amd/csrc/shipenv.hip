@@ -2710,6 +2710,63 @@ struct RolloutArgs {
     int32_t* status;
 };
 
+// One step of a private env copy from its drawn block d (words 1-3: u_fuel, u_gate, u_type)
+// and, for a partial loss or an arrival, the block at (t, slot_b): three beta uniforms, the
+// new destination. The step of a rollout attempt and of an MCTS tree step (mcts.h). A
+// raising step (p.e != SE_ERR_OK) leaves s untouched.
+__device__ __forceinline__ Pending drawn_step(const LdsWorld& w, Ship& s, const Key& key, uint32_t t,
+                                              uint32_t slot_b, const U4& d, int ty, int va, int vb) {
+    Pending p = env_begin<true, false>(w, s, SE_ERR_OK, ty, va, vb, (double)d.v[1], 0.0, d.v[2]);
+    if (p.e != SE_ERR_OK) return p;
+    const int total_kind = d.v[3] > kTypeHi ? kLossTotal : kLossPartial;
+    const int kind = d.v[3] < kTypeLo ? kLossNone : total_kind;
+    uint32_t med = 0u;
+    int nd = 0;
+    if ((p.fires & (kind == kLossPartial)) | p.arrive) {
+        const U4 e = draw(key, t, slot_b);
+        const uint32_t lo = min(e.v[0], e.v[1]), hi = max(e.v[0], e.v[1]);
+        med = max(lo, min(hi, e.v[2]));
+        nd = pick_other(e.v[3], w.P, s.dest);
+    }
+    env_finish(s, p, kind, beta_part(med, s.cargo), nd, p.fires, p.arrive);
+    return p;
+}
+
+// _rollout (agents/mcts.py:211-238) on the private copy s with the draws of `key`; returns
+// SE_ROLL_*. A raising sample_action leaves its type (SE_SAMPLE_*) in sample_type.
+__device__ __forceinline__ int32_t rollout_run(const LdsWorld& w, Ship& s, const Key& key, int32_t max_steps,
+                                               int32_t max_attempts, double& total, int32_t& steps,
+                                               int& sample_type) {
+    total = 0.0;
+    steps = 0;
+    sample_type = 0;
+    int32_t status = SE_ROLL_ATTEMPTS;
+    for (int32_t k = 0; k < max_attempts; ++k) {
+        if (steps >= max_steps) {  // while not done and steps < max_rollout_steps (:225)
+            status = SE_ROLL_MAX_STEPS;
+            break;
+        }
+        const U4 d = draw(key, (uint32_t)k, kSlotRollout);
+        int ty, va, vb;
+        sample_action(w, s, d.v[0], ty, va, vb);
+        if (ty < 0) {
+            sample_type = ty;
+            status = SE_ROLL_RAISED;
+            break;
+        }
+        const Pending p = drawn_step(w, s, key, (uint32_t)k, kSlotRolloutB, d, ty, va, vb);
+        if (p.e != SE_ERR_OK) continue;  // except Exception: continue (state untouched)
+        total += p.r;  // total_reward += reward (:229)
+        steps += 1;
+        if (p.dead) {
+            status = SE_ROLL_DONE;
+            break;
+        }
+    }
+    if (status == SE_ROLL_ATTEMPTS && steps >= max_steps) status = SE_ROLL_MAX_STEPS;
+    return status;
+}
+
 __global__ __launch_bounds__(kBlock) void rollout_kernel(RolloutArgs A) {
     extern __shared__ uint32_t lds[];
     const LdsWorld w = stage_world(A.world, A.dims, lds);
@@ -2723,42 +2780,11 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(RolloutArgs A) {
             continue;
         }
         Ship s{A.st.x[i], A.st.y[i], A.st.fuel[i], A.st.cargo[i], A.st.origin[i], A.st.dest[i]};
-        const Key key = env_key(A.seed, A.rollout_base + r);
-        double total = 0.0;
-        int32_t steps = 0, status = SE_ROLL_ATTEMPTS;
-        for (int32_t k = 0; k < A.max_attempts; ++k) {
-            if (steps >= A.max_steps) {  // while not done and steps < max_rollout_steps (:225)
-                status = SE_ROLL_MAX_STEPS;
-                break;
-            }
-            const U4 d = draw(key, (uint32_t)k, kSlotRollout);
-            int ty, va, vb;
-            sample_action(w, s, d.v[0], ty, va, vb);
-            if (ty < 0) {
-                status = SE_ROLL_RAISED;
-                break;
-            }
-            Pending p = env_begin<true, false>(w, s, SE_ERR_OK, ty, va, vb, (double)d.v[1], 0.0, d.v[2]);
-            if (p.e != SE_ERR_OK) continue;  // except Exception: continue (state untouched)
-            const int total_kind = d.v[3] > kTypeHi ? kLossTotal : kLossPartial;
-            const int kind = d.v[3] < kTypeLo ? kLossNone : total_kind;
-            uint32_t med = 0u;
-            int nd = 0;
-            if ((p.fires & (kind == kLossPartial)) | p.arrive) {
-                const U4 e = draw(key, (uint32_t)k, kSlotRolloutB);
-                const uint32_t lo = min(e.v[0], e.v[1]), hi = max(e.v[0], e.v[1]);
-                med = max(lo, min(hi, e.v[2]));
-                nd = pick_other(e.v[3], w.P, s.dest);
-            }
-            env_finish(s, p, kind, beta_part(med, s.cargo), nd, p.fires, p.arrive);
-            total += p.r;  // total_reward += reward (:229)
-            steps += 1;
-            if (p.dead) {
-                status = SE_ROLL_DONE;
-                break;
-            }
-        }
-        if (status == SE_ROLL_ATTEMPTS && steps >= A.max_steps) status = SE_ROLL_MAX_STEPS;
+        double total;
+        int32_t steps;
+        int sample_type;
+        const int32_t status = rollout_run(w, s, env_key(A.seed, A.rollout_base + r), A.max_steps,
+                                           A.max_attempts, total, steps, sample_type);
         A.ret[r] = total;
         A.steps[r] = steps;
         A.status[r] = status;
@@ -3613,6 +3639,7 @@ int se_host_destroy(se_host* h) {
 
 // the fused DQN policy step (same translation unit: world image, env handle, Philox)
 #include "qpolicy.h"
+#include "mcts.h"
 #include "replay.h"
 #include "qtrain.h"
 #include "server.h"
