@@ -239,7 +239,7 @@ int se_server_destroy(se_server* s);
 
 /* Host-resident environments (no device, no HIP call): the N = 1 drop-in
  * shipping.Environment steps here by default (shippingenv_amd/shipping/_host.py), with the
- * step kernels' own per-env code compiled for the host (replay_env in shipenv.hip), so a
+ * step kernels' own per-env code compiled for the host (replay_env in env_core.h), so a
  * reference step() costs one C call instead of a kernel launch and a stream synchronise.
  * The state buffers are host memory; no alignment is required.
  *   se_host_create / se_host_set_ports   Environment.__init__ + add_port (:29-65)

@@ -16,9 +16,17 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "shipenv.hip")
 MAPSRC = os.path.join(HERE, "csrc", "mapload.cpp")  # host-only: the JPEG map loader
-DEPS = [SRC, MAPSRC, os.path.join(HERE, "csrc", "philox.h"), os.path.join(HERE, "csrc", "qpolicy.h"), os.path.join(HERE, "csrc", "replay.h"), os.path.join(HERE, "csrc", "server.h"),
-        os.path.join(HERE, "csrc", "qtrain.h"), os.path.join(HERE, "csrc", "mcts.h"),
-        os.path.join(ROOT, "include", "shipenv.h")]
+
+
+def _deps():
+    """Every source under csrc/ and the public header: shipenv.hip is one translation unit of
+    many fragments, and a fragment missing here would leave a stale library "up to date"."""
+    found = [os.path.join(d, f) for d, _, files in os.walk(os.path.join(HERE, "csrc")) for f in files
+             if f.endswith((".hip", ".cpp", ".h"))]
+    return sorted(found) + [os.path.join(ROOT, "include", "shipenv.h")]
+
+
+DEPS = _deps()
 OUT = os.path.join(HERE, "_lib", "libshipenv_hip.so")
 ARCH = os.environ.get("SHIPENV_OFFLOAD_ARCH", "gfx950")
 

@@ -1,5 +1,13 @@
-// mcts.h — one MCTS decision per env (agents/mcts.py:240-292, MCTSAgent.choose_action),
-// included by shipenv.hip: se_mcts_create / se_mcts_choose / se_mcts_destroy.
+#pragma once
+// mcts.h — one MCTS decision per env (agents/mcts.py:240-292, MCTSAgent.choose_action):
+// the tree in a buffer the handle owns, its kernel, and se_mcts_create / se_mcts_choose /
+// se_mcts_destroy.
+//
+// A fragment of shipenv.hip's translation unit, included at its end after qpolicy.h: not a
+// stand-alone header. Uses world.h (WorldDims, LdsWorld, stage_world, sqrt_rn), env_core.h
+// (Ship, Pending, env_key), rollout.h (sample_action, drawn_step, rollout_run), philox.h, and
+// the host side's se_env, check_ready, fail, HIP_TRY, DeviceGuard, aligned16,
+// allow_dynamic_lds and lds_bytes.
 //
 // One lane runs choose_action for one env: S = num_simulations sequential simulations
 // (selection by UCB1, one expansion, a random rollout, backpropagation) on a private Ship
@@ -40,7 +48,6 @@
 // touch neighbouring addresses ("MCTS decisions"): a 16-byte record per node and
 // env (the node word, the action index, visits) and its f64 total_reward. Children are found
 // by scanning the nodes for a parent index.
-#pragma once
 
 namespace {
 

@@ -1,7 +1,14 @@
-// qpolicy.h — the DQN policy step fused on MFMA.
+#pragma once
+// qpolicy.h — the DQN policy step fused on MFMA: the
+// network handle se_qnet with its packed weights (QnetDims), the policy kernels,
+// launch_policy / launch_policy_f32 and the se_qnet_* / se_policy_* entry points.
 //
-// Part of shipenv.hip's translation unit (included at its end): it shares the
-// world image, the env handle and Philox. Reference: agents/dqn.py DQNNetwork
+// A fragment of shipenv.hip's translation unit, included at its end after the host
+// side: not a stand-alone header. Uses world.h (WorldDims, LdsWorld, stage_world,
+// world_view), env_core.h (env_key), philox.h, and the host side's se_env,
+// check_ready, fail, HIP_TRY, DeviceGuard, allow_dynamic_lds, lds_bytes and kBlock.
+//
+// Reference: agents/dqn.py DQNNetwork
 // (:21-33: fc1 6+4P -> 128, relu, fc2 128 -> 128, relu, fc3 128 -> A = 4+P+250)
 // and choose_action (:177-203), on preprocess_state rows (utils/preprocessing.py:25-62).
 //

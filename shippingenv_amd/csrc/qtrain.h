@@ -1,6 +1,15 @@
-// qtrain.h — the DQN update fused on MFMA in f32 arithmetic.
+#pragma once
+// qtrain.h — the DQN update fused on MFMA in f32 arithmetic: the
+// trainer handle se_qtrain, the tile kernel (forward, loss, backward), the reduce +
+// Adam kernel, and the se_qtrain_* entry points.
 //
-// Part of shipenv.hip's translation unit (included at its end, after replay.h).
+// A fragment of shipenv.hip's translation unit, included at its end after replay.h:
+// not a stand-alone header. Uses world.h (WorldDims, LdsWorld, world_view),
+// env_core.h (env_key), step_io.h (kRecDone), qpolicy.h (se_qnet, QnetDims, the bf16
+// split and MFMA helpers), replay.h (se_replay, Ring, the pick_* sampler, ship_col),
+// and the host side's se_env, check_ready, fail, HIP_TRY, DeviceGuard and
+// allow_dynamic_lds.
+//
 // Reference: agents/dqn.py DQNAgent.update (:206-245) on a sampled minibatch.
 // It computes q = DQNNetwork(states)[a] and y = r + gamma * max target(next_states) * (1 - done),
 // then nn.MSELoss and backward, then Adam (lr, betas (0.9, 0.999), eps 1e-8).

@@ -1,6 +1,16 @@
-// replay.h — the DQN experience replay ring on the device.
+#pragma once
+// replay.h — the DQN experience replay ring on the device: the
+// ring se_replay, its begin / end passes, the Feistel sampler, and the recording
+// entry points se_step_record and se_policy_record*.
 //
-// Part of shipenv.hip's translation unit (included at its end, after qpolicy.h).
+// A fragment of shipenv.hip's translation unit, included at its end after mcts.h:
+// not a stand-alone header. Uses world.h (WorldDims, LdsWorld, world_view),
+// env_core.h (Ship, env_key, reset_ship), step_io.h (the StepRecord contract that
+// step_kernel's record instantiation fills: kRecDone, kRecMaxIters), philox.h,
+// qpolicy.h (se_qnet, PolicyRecord, launch_policy / launch_policy_f32), and the
+// host side's se_env, launch_step, check_ready, fail, HIP_TRY, DeviceGuard,
+// aligned16, grid_for and kBlock.
+//
 // Reference: agents/dqn.py DQNAgent.remember (:117-123, a deque(maxlen=memory_size)
 // of (state, action, reward, next_state, done)) and the minibatch of update()
 // (:213-224: random.sample(memory, batch_size), np.vstack of the preprocess_state

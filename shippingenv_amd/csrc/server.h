@@ -1,7 +1,14 @@
+#pragma once
 // server.h — the N = 1 drop-in's GPU stepper as one persistent wave (VERDICT r05
-// item 8).
+// item 8): server_kernel, the handle se_server, se_host_alloc / se_host_free and the
+// se_server_* entry points.
 //
-// Part of shipenv.hip's translation unit (included at its end). Reference callers: the agents
+// A fragment of shipenv.hip's translation unit, included at its end after qtrain.h: not a
+// stand-alone header. Uses world.h (WorldDims, LdsWorld, stage_world), env_core.h (Ship,
+// Pending, replay_env), shipenv.hip's kFuelInit, and the host side's se_env, fail, HIP_TRY,
+// DeviceGuard, allow_dynamic_lds and lds_bytes.
+//
+// Reference callers: the agents
 // step one env at a time, once per decision (agents/dqn.py:287) and ~500 times per MCTS
 // decision (agents/mcts.py:228-236), each step() a few bytes in and out
 // (environment.py:359-376). As a kernel launch plus a stream synchronise per step that is

@@ -1,0 +1,333 @@
+#pragma once
+// step_seq.h — se_step_seq's fused run of steps with the state in registers:
+// Carried, the state-only step_group_state, stock_by_code, step_seq_kernel and
+// the partial last group's step_tail_seq_kernel.
+//
+// A fragment of shipenv.hip's translation unit, included inside its anonymous
+// namespace where this text stood: not a stand-alone header.
+// Uses world.h (the image's tables, staging), env_core.h (env_key, beta_part),
+// step_io.h (StepArgs, Group, At, ld4_full / st4*_full), step_group.h (BlockStats,
+// Finished), step_agent.h (the packed helpers, early_draws, step_group_agent: the
+// run's last step) and step_kernel.h (step_tail_envs).
+
+// The state-only step: a step of a fused sequence before its last, for a full group, Philox
+// draws, no auto-reset. Nothing can read an inner step's reward, done or err, and the next state
+// needs neither the out-of-fuel flag (a dead ship keeps moving) nor which error was raised, only
+// whether one was. So there is no reward, no out-of-fuel compare, and the action's checks are one
+// bit. The state arithmetic, its order and every Philox counter are step_group_agent's.
+// Position, origin and dest live in Carried from step to step, one register per env, so
+// consecutive steps neither unpack nor pack bytes; fuel, cargo and the action are G's (of G the
+// step touches f, c and a only). The cell code under the ship is carried too (after a move
+// it is the byte the ground test read at the cell moved to), so a step makes one cell lookup per
+// env, with the table's LDS address riding in the dot product (lds_cell). The complements of the
+// action-range compares are s_not of their lane masks (with_complement). The caller draws FUEL
+// and GATE together (fb, gb: philox.h, draw2). The ranked LOSS draw is step_group_agent's, line
+// for line: as a shared helper it compiled to another instruction order in both steps.
+// The take and the arrival test run only for a wave that needs them (two ballots per step,
+// scalar branches). Ships are mostly at sea, so most wave-steps run neither
+// (profiles/seq_guard/freq.json).
+struct Carried {
+    uint32_t pos[4];  // x | y << 16
+    int org[4], dst[4];
+    uint32_t code[4];   // the cell code under the ship, w.cell[cell_of(pos)]
+    const int2* take;   // the block's stocks by cell code (stock_by_code), the same for every env
+};
+template <bool kNt>
+__device__ __forceinline__ void step_group_state(const LdsWorld& w, const Key& qk, uint32_t t, const U4& fb,
+                                                 const U4& gb, Group<false, false, kNt>& G, Carried& U) {
+    const int P = w.P;
+    const uint32_t lim = (uint32_t)(w.H - 1) | ((uint32_t)(w.W - 1) << 16);
+    const uint32_t wh = (uint32_t)w.W | (1u << 16);
+    const uint32_t pm1 = P > 0 ? (uint32_t)(P - 1) : 0u;  // clamp for table reads whose value an error discards
+    // The take guard. A take passes only for a ship on a port cell, so a wave none of whose
+    // envs has a take action on a non-water cell (code != 0: wider than "a port's code", so
+    // ground and codes past P only send their wave here) skips the whole take: the stock
+    // read, the amount checks, the cargo add and the fuel's f64 conversion. The vote is a
+    // ballot, so the branch is scalar; it reads this step's actions and the codes before
+    // the move. A passed take changes only cargo and fuel, and its env neither moves nor
+    // selects, so it is applied here and the step below runs without it: cargo is what the
+    // full step's `tc_ok ? cargo + amount : cargo` gives, and fuel reaches the fuel update as
+    // fuel + amount, to which that update adds -0.0, which changes no bit of any value.
+    bool take_any = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) take_any |= (G.a[j] >= 4 + P) & (U.code[j] != 0);
+    if (__builtin_amdgcn_ballot_w64(take_any) != 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int act = G.a[j];
+            const bool lt_tc = act < 54 + P;
+            const int amount = act - (lt_tc ? 4 + P : 54 + P);
+            // the stocks by the carried cell code, zero off a port: 0 < amount <= stock
+            // then holds at a port with the stock only (and never when P == 0)
+            const int2 st2 = U.take[U.code[j]];
+            const int stock = lt_tc ? st2.y : st2.x;
+            const bool ok_take = (act >= 4 + P) & (amount > 0) & (amount <= stock);
+            G.c[j] = (ok_take & lt_tc) ? G.c[j] + amount : G.c[j];
+            G.f[j] = (ok_take & !lt_tc) ? G.f[j] + (double)amount : G.f[j];
+        }
+    }
+    uint32_t pos[4];
+    int dst[4], cg[4];
+    bool do_move[4], moved[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        // [0,4) moves (-4..-1 wrap), [4, 4+P) SELECT; the takes are done
+        const int act = G.a[j];
+        const bool bad = act < -4;
+        const Pred2 mv = with_complement(act < 4), sel = with_complement(act < 4 + P);
+        const int val = act - 4;  // only a select reads it
+        const uint32_t dxy = w.moves[act & 3];
+        const uint32_t p = U.pos[j];
+        dst[j] = U.dst[j];
+        cg[j] = G.c[j];
+        // MOVE (_move_ship :273-339)
+        const uint32_t np = pk_add_u16(p, dxy);
+        const bool inb = pk_min_u16(np, lim) == np;  // _is_within_map (:284); -1 wraps to 0xffff
+        const bool nodest = dst[j] == SE_NONE;       // :276
+        const uint32_t cp = (!nodest & inb) ? np : p;  // in-range cell for the lookup
+        uint32_t code_cp = lds_cell(lds_address(w.cell), cp, wh);
+        // carried as a full register (as a byte it is masked again before every select)
+        asm("" : "+v"(code_cp));
+        const bool ground = code_cp == kCellGround;  // :293
+        // step_group_agent's error cascade as its one bit: no check of the action's own type
+        // failed (mask arithmetic, no ?: : a branch here would take the LDS lookups with it).
+        // A take is not among them: the take guard has applied it, and nothing below reads
+        // whether a take passed.
+        const bool same = U.org[j] == val;
+        const bool ok_mv = mv.t & !nodest & inb;
+        const bool ok_sel = mv.f & sel.t & !same;
+        const bool ok = !bad & (P != 0) & (ok_mv | ok_sel);
+        do_move[j] = ok & mv.t;
+        moved[j] = do_move[j] & !ground;
+        const bool sel_ok = ok & mv.f & sel.t;
+        pos[j] = moved[j] ? cp : p;
+        U.code[j] = moved[j] ? code_cp : U.code[j];  // the ground test's read
+        dst[j] = sel_ok ? val : dst[j];
+    }
+    uint32_t fire = 0, arrive = 0;
+    // The arrival guard. An arrival (:325) happens on a port's cell, and the world image
+    // stamps every port's cell with a non-zero code, so a wave none of whose movers is on
+    // a non-water cell after the move has no arrival and reads no destination position.
+    // The vote is a ballot (a scalar branch) over the codes as the move left them. The
+    // test itself stays the position compare: two ports may share a cell, and dest may
+    // hold anything a caller loaded. (A mover selects nothing, so dst is still its dest.)
+    bool arrive_any = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) arrive_any |= do_move[j] & (U.code[j] != 0);
+    if (__builtin_amdgcn_ballot_w64(arrive_any) != 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            arrive |= (uint32_t)(do_move[j] & (pos[j] == w.pos[min((uint32_t)dst[j], pm1)])) << j;
+    }
+    double f[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        // fuel cost (:103-104); a ship that does not move adds -0.0, which leaves every value as it is
+        const double scale = 1.0 + (-0.1 + (double)fb.v[j] * kFifthPerWord);
+        f[j] = G.f[j] + (moved[j] ? -scale : -0.0);
+        // the gate (:318-323), as step_group_agent tests it
+        const uint32_t thr = w.gate_thr[min(max(cg[j], 0), 50)];
+        const bool fires = do_move[j] & (cg[j] > 0) & (gb.v[j] <= thr);
+        fire |= (uint32_t)fires << j;
+    }
+    // the flags travel as opaque VGPR bit masks (no lane masks live in SGPR pairs
+    // across the draw blocks below)
+    asm volatile("" : "+v"(fire), "+v"(arrive));
+    int org[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        org[j] = U.org[j];
+        U.pos[j] = pos[j];
+        G.f[j] = f[j];
+    }
+    // cargo loss and arrival, only in waves with a firing gate / an arrival
+    if (fire) {
+        uint32_t lt[4], v1[4], v2[4], v3[4];
+        const uint32_t rk[4] = {0u, fire & 1u, (uint32_t)__popc(fire & 3u), (uint32_t)__popc(fire & 7u)};
+        U4 rr = draw(qk, t, loss_slot(0));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            lt[j] = rr.v[0];
+            v1[j] = rr.v[1];
+            v2[j] = rr.v[2];
+            v3[j] = rr.v[3];
+        }
+#pragma unroll
+        for (uint32_t q = 1; q < 4; ++q) {
+            if (__popc(fire) > q) {
+                rr = draw(qk, t, loss_slot(q));
+#pragma unroll
+                for (int j = (int)q; j < 4; ++j) {
+                    const bool take = rk[j] >= q;
+                    lt[j] = take ? rr.v[0] : lt[j];
+                    v1[j] = take ? rr.v[1] : v1[j];
+                    v2[j] = take ? rr.v[2] : v2[j];
+                    v3[j] = take ? rr.v[3] : v3[j];
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            // beta = the median of the three words * 2^-32 (the conversion is monotone)
+            const uint32_t lo = min(v1[j], v2[j]), hi = max(v1[j], v2[j]);
+            const uint32_t med = max(lo, min(hi, v3[j]));  // v_med3_u32
+            const int part = beta_part(med, cg[j]);
+            const int some = lt[j] > kTypeHi ? cg[j] : part;
+            const int loss = lt[j] < kTypeLo ? 0 : some;
+            const bool fj = (fire >> j) & 1u;
+            cg[j] = fj ? cg[j] - loss : cg[j];
+        }
+    }
+    if (arrive) {
+        const U4 ab = draw(qk, t, kSlotArrive);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool aj = (arrive >> j) & 1u;
+            const int nd = pick_other(ab.v[j], P, dst[j]);
+            cg[j] = aj ? 0 : cg[j];
+            org[j] = aj ? dst[j] : org[j];
+            dst[j] = aj ? nd : dst[j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        U.org[j] = org[j];
+        U.dst[j] = dst[j];
+        G.c[j] = cg[j];
+    }
+}
+
+// The stocks by cell code for the state-only steps' take checks: 256 (fuel, cargo) pairs,
+// port i's at code i + 1 and zeros at every other code (0 water, kCellGround, codes past P),
+// so `0 < amount <= stock` is false wherever the ship is on no port. One entry per thread of
+// the block, read from the staged image; the caller holds the barrier.
+constexpr size_t kStockByCodeBytes = 256 * sizeof(int2);
+static_assert(kStepBlock == 256, "stock_by_code: one cell code per thread");
+__device__ __forceinline__ void stock_by_code(const LdsWorld& w, int2* take) {
+    const uint32_t k = threadIdx.x - 1u, P = (uint32_t)w.P;
+    const int2 s = w.stock[min(k, P > 0 ? P - 1 : 0u)];  // P = 0: a word of the image, unused
+    take[threadIdx.x] = k < P ? s : make_int2(0, 0);
+}
+
+// se_step_seq without auto-reset, fused: `steps` consecutive steps of the agent path in one
+// launch, on step_kernel's grid and ownership. Nothing outside the stream can observe the
+// state between two steps of one sequence, and a step reads only x, y, origin, dest, cargo,
+// fuel and its action, so a group is loaded once, stepped `steps` times in registers
+// (counter A.t + k, action row k at A.act + k * ld) and stored once, with the last step's
+// reward, done and err. Against a launch per step that leaves out, per
+// step, the launch, the world staging, 32 B of state loads and 38 B of stores per env; what a
+// step still moves is its 4 B action. Row k + 1 is loaded before step k's arithmetic, so its
+// latency (rows are read once, from HBM) hides behind the step. iters > 1: the group loop is
+// the outer one.
+// Only the last step's reward, done and err exist anywhere, so steps 0 .. steps - 2 run the
+// state-only step (step_group_state), with x | y, origin and dest unpacked once before them
+// and packed once after, and step steps - 1 alone runs the full one (step_group_agent<kKeep>).
+// Every launch of a split run therefore ends with a full step; steps == 1 is the full step by
+// itself.
+template <bool kNt>
+__global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4))) void step_seq_kernel(
+    StepArgs A, int32_t steps, int64_t ld) {
+    extern __shared__ uint32_t lds[];
+    if (steps <= 0) return;  // nothing to store (the host launches no empty run)
+    const int64_t full = A.n >> 2;
+    const int64_t first = (int64_t)blockIdx.x * A.iters * kStepBlock;  // block-uniform first group
+
+    const Staged st = stage_issue(A.world);
+    __builtin_amdgcn_sched_barrier(0);
+    // first group: step_kernel's clamped, unconditional load (state and action row 0)
+    Group<false, false, kNt> G;
+    {
+        const int64_t last = full - 1 - first;  // block-uniform
+        const uint32_t lane = last < (int64_t)threadIdx.x ? (uint32_t)(last < 0 ? 0 : last) : threadIdx.x;
+        G.template load<true>(A, At<true>{last < 0 ? full - 1 : first, 0, A.n}, lane);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const LdsWorld w = stage_finish(A.world, A.dims, lds, st);
+    // the state-only steps' take checks: the stocks by cell code, behind the staged image
+    int2* const take = reinterpret_cast<int2*>(lds + A.dims.padded());
+    if (steps > 1) {  // launch-uniform
+        stock_by_code(w, take);
+        __syncthreads();
+    }
+
+    BlockStats bs;
+    Finished F;
+    for (int64_t i = 0; i < A.iters; ++i) {
+        const int64_t g0 = first + i * kStepBlock, g = g0 + threadIdx.x;
+        if (g >= full) break;  // no barrier below
+        if (i > 0) {
+            // the lane opaque: the loads' per-lane addresses are computed here, once per group,
+            // not kept in ~20 VGPRs across the step loop for the next group's sake
+            uint32_t lane = threadIdx.x;
+            asm volatile("" : "+v"(lane));
+            G.template load<true>(A, At<true>{g0, 0, A.n}, lane);
+        }
+        const At<true> at{g0, g * 4, A.n};
+        const uint32_t tl = A.t + (uint32_t)(steps - 1);  // the last step's counter
+        if (steps > 1) {
+            // steps 0 .. steps - 2, state only: x | y, origin and dest one register per env
+            Carried U;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                U.pos[j] = unpack_pos(G.x, G.y, j);
+                U.org[j] = byte_of(G.org, j);
+                U.dst[j] = byte_of(G.dst, j);
+                U.code[j] = w.cell[cell_of(U.pos[j], (uint32_t)w.W | (1u << 16))];
+            }
+            U.take = take;
+            // the step-invariant parts of the quad's FUEL and GATE blocks (philox.h, draw2),
+            // opaque so the loop keeps them in registers as computed here
+            const Key qk = env_key(A.seed, (A.env_base + g * 4) >> 2);
+            PairInv inv = pair_invariants(qk);
+            asm volatile("" : "+v"(inv.hi[0]), "+v"(inv.lo[0]), "+v"(inv.hi[1]), "+v"(inv.lo[1]));
+            const int32_t* row = A.act;
+            for (uint32_t t = A.t; t != tl; ++t) {
+                // the next row's actions (there is one: the last step follows)
+                row += ld;
+                int32_t nxt[4];
+                ld4_full<kNt>(row, g0, nxt);
+                const U4x2 fg = draw2(qk, inv, t);
+                step_group_state(w, qk, t, fg.fuel, fg.gate, G, U);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
+            }
+            // back into the Group's packed bytes
+            pack_pos(U.pos, G.x, G.y);
+            G.org = G.dst = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                G.org |= (uint32_t)(U.org[j] & 0xff) << (8 * j);
+                G.dst |= (uint32_t)(U.dst[j] & 0xff) << (8 * j);
+            }
+        }
+        // the last step in full: its reward, done and err are the run's
+        StepOut O;
+        step_group_agent<false, true, kNt, false, false, true>(A, w, G, at, bs, F, early_draws<false>(A, g * 4, tl), tl, &O);
+        const se_state& S = late_args().st;
+        __builtin_amdgcn_sched_barrier(0);  // the fuel halves back to back (store_moved)
+        st4u8_full(S.x, g0, G.x);
+        st4u8_full(S.y, g0, G.y);
+        st4_full(S.fuel, g0, G.f);
+        st4u8_full(S.done, g0, O.dn);
+        st4u8_full(reinterpret_cast<uint8_t*>(S.err), g0, O.ee);
+        __builtin_amdgcn_sched_barrier(0);
+        st4u8_full(S.origin, g0, G.org);
+        st4u8_full(S.dest, g0, G.dst);
+        st4_full(S.cargo, g0, G.c);
+        st4_full(S.reward, g0, O.rw);
+    }
+}
+
+// The partial last group of a fused sequence: one thread steps its at most 3 envs `steps`
+// times with step_tail_envs, loading and storing per step.
+__global__ __launch_bounds__(64) void step_tail_seq_kernel(StepArgs A, int32_t steps, int64_t ld) {
+    if (threadIdx.x != 0) return;
+    const LdsWorld w = world_view(A.dims, A.world);
+    const int32_t* act = A.act;
+    const uint32_t t0 = A.t;
+    for (int32_t k = 0; k < steps; ++k) {
+        A.act = act + (int64_t)k * ld;
+        A.t = t0 + (uint32_t)k;
+        step_tail_envs<false, false, false>(A, w);
+    }
+}

@@ -3,7 +3,7 @@
 The reference steps one env per call (agents/dqn.py:287, agents/mcts.py:228-236). On the
 GPU that is a launch plus a stream synchronise per step, ~18 us, where the reference's
 Python step takes ~10 us. The host stepper runs the step kernels' own per-env code
-(``replay_env`` in csrc/shipenv.hip, compiled for the host: se_host_step_replay) on an
+(``replay_env`` in csrc/env_core.h, compiled for the host: se_host_step_replay) on an
 88-byte state block in host memory: one C call per step, no device. It is not a
 fallback: the library is the same, a missing library still raises
 NativeLibraryError, and ``SHIPENV_STEPPER=gpu`` selects the kernel (DeviceStepper).

@@ -1,6 +1,6 @@
 """Full-size (N = 2^20) parity of the kernels the bench times, in the state mix it times.
 
-bench.py's headline times `step_kernel<..., kSeq = true>` (VecEnv.step_seq) after a
+bench.py's headline times `step_seq_kernel` (VecEnv.step_seq, the fused run) after a
 1000-step pre-roll from reset; config 4 times the auto-reset kernel (64 ports) after the
 same pre-roll. These tests run exactly those sequences on 2^20 envs and check sampled
 slices of whole quads bit for bit against the C oracle (tests only) on the same global

@@ -716,7 +716,7 @@ def test_step_seq_equals_step_calls(auto, n):
 @pytest.mark.parametrize("P", [5, 64])
 def test_agent_replay_need_draw_restores_state(P, water):
     """tapes that lack a variate the step needs. se_step_agent_replay answers
-    SE_ERR_NEED_DRAW (10) and puts back the env's old state (shipenv.hip: the group restore
+    SE_ERR_NEED_DRAW (10) and puts back the env's old state (step_agent.h: the group restore
     after its stores, full groups and the n % 4 tail); the typed replay kernel and the host
     build of the same code (se_host_step_replay, the drop-in's stepper) must agree bit for
     bit on state, reward, done, err and the `used` bits, and a NEED_DRAW env must equal its

@@ -1,5 +1,5 @@
 """The host-compiled step (se_host_step_replay / se_host_reset_to: the step kernels' own
-per-env code, replay_env in csrc/shipenv.hip, built for the host) against the reference's
+per-env code, replay_env in csrc/env_core.h, built for the host) against the reference's
 golden records, and the drop-in shipping.Environment on it against the reference's seeded
 traces. No GPU: this is the product's N = 1 path (the default stepper of the drop-in);
 tests/test_compat_gpu.py checks it against the kernel bit for bit."""

@@ -61,6 +61,41 @@ def test_misuse_is_a_status_not_a_crash(lib):
         _native.check(lib.se_bind(None, None))
 
 
+def test_every_source_is_a_build_dependency(monkeypatch, tmp_path):
+    """build.DEPS holds every source under csrc/ (shipenv.hip's fragments included), and a
+    header newer than the library makes it stale. The timestamps are a temporary copy's."""
+    from shippingenv_amd import build
+
+    csrc = os.path.join(ROOT, "shippingenv_amd", "csrc")
+    sources = [os.path.join(d, f) for d, _, files in os.walk(csrc) for f in files
+               if f.endswith((".hip", ".cpp", ".h"))]
+    assert len(sources) >= 17  # shipenv.hip, mapload.cpp, philox.h, 9 + 5 fragments
+    deps = {os.path.realpath(d) for d in build.DEPS}
+    for s in sources:
+        assert os.path.realpath(s) in deps, s
+    assert os.path.realpath(os.path.join(ROOT, "include", "shipenv.h")) in deps
+
+    copies = []
+    for k, d in enumerate(build.DEPS):
+        c = tmp_path / ("%02d_%s" % (k, os.path.basename(d)))
+        c.write_text("")
+        os.utime(c, (1000, 1000))
+        copies.append(str(c))
+    out = tmp_path / "libshipenv_hip.so"
+    out.write_text("")
+    os.utime(out, (2000, 2000))
+    (tmp_path / "libshipenv_hip.so.cmd").write_text(" ".join(build._flags()))
+    monkeypatch.setattr(build, "DEPS", copies)
+    monkeypatch.setattr(build, "OUT", str(out))
+    monkeypatch.setattr(build, "STAMP", str(out) + ".cmd")
+    assert build.up_to_date()
+    for c in copies:  # each one alone, the fragments as much as shipenv.hip
+        os.utime(c, (3000, 3000))
+        assert not build.up_to_date(), c
+        os.utime(c, (1000, 1000))
+    assert build.up_to_date()
+
+
 def test_product_path_has_no_fallback(monkeypatch, tmp_path):
     """A missing library raises instead of silently stepping on the CPU."""
     from shippingenv_amd import _native
