@@ -348,6 +348,89 @@ int se_mcts_choose(se_mcts* m, int32_t simulations, double c_param, int32_t max_
                    int32_t* status, se_mcts_node* tree, int32_t* tree_count, void* stream);
 int se_mcts_destroy(se_mcts* m);
 
+/* Batched tabular SARSA (agents/sarsa.py): one learner with one dense f64 Q-table in device
+ * memory, the env's n envs stepping it together. One se_sarsa_step runs the body of train's
+ * inner loop (:255-272) for every env: a fresh env first takes choose_action(state) as its
+ * pending action; _try_action (:201-220) steps the pending action and, if it raises, repeats
+ * sample_action() + step, max_attempts attempts in all (the reference loops forever);
+ * next_action = choose_action(next_state) (:135-165); the update (:187-195)
+ *   new = q + lr * ((reward + gamma * next_q) - q)
+ * in f64, unfused, in that order, with the step's unrounded f64 reward, keyed by (the state
+ * before, the pending action as chosen, also where that action raised and a sampled one was
+ * stepped), without terminal masking; then done, ep_len >= max_steps (max_steps > 0; 0: no
+ * such cut) or a status other than OK restart the env: a reset (:227-243) with fresh origin
+ * and dest, marked fresh. A status other than OK writes nothing to the table. With one port
+ * (the reference's reset never returns) the restart leaves the destination None.
+ *
+ * choose_action: with u = word * 2^-32, u < epsilon (strict) explores with sample_action() on
+ * that state; else the first strict maximum of Q, from -inf, over _get_possible_actions
+ * (:81-133) in its order: SELECT 0..P-1, the moves (0,-1), (0,1), (-1,0), (1,0), and at a port
+ * (the first index whose position matches) TAKE_CARGO 1..min(20, stock), TAKE_FUEL 1..min(20,
+ * stock). An untouched table answers SELECT 0. Where nothing compares greater (NaN, -inf) it
+ * is sample_action(), as in the reference.
+ *
+ * Table layout. discretize_state (utils/preprocessing.py:65-90) reads the fuel for both of its
+ * buckets ("cargo" in the state dict is the fuel, environment.py:206): cargo_bucket =
+ * min(int(fuel / 10), 4), fuel_bucket = min(int(fuel / 20), 4), f64 divisions truncated toward
+ * zero. For fuel > -10 seven pairs occur, the fuel class: 0 (0,0), 1 (1,0), 2 (2,1), 3 (3,1),
+ * 4 (4,2), 5 (4,3), 6 (4,4). Fuel <= -10 is outside the domain (a move burns at most 1.1 from
+ * a non-negative fuel) and is clamped to class 0, as are coordinates and port indices out of
+ * range to the nearest valid value / None, so that the index is always in range.
+ *   row   = (((x * W + y) * 7 + class) * (P + 1) + origin + 1) * (P + 1) + dest + 1   (None -> 0)
+ *   entry = row * A + slot,   A = P + 4 + cmax + 20,   cmax = max(20, the largest port_cargo)
+ *   slot: SELECT p at p; the four moves at P..P+3 in the order above; TAKE_CARGO m at P+3+m;
+ *         TAKE_FUEL m at P+3+cmax+m.
+ * The table (rows * A doubles) is the caller's and zero-initialised by it: the reference's
+ * dict answers 0.0 for a key it lacks.
+ *
+ * Many envs, one table: every Q read of a vector step sees the table after all writes of the
+ * step before, and where several envs update one entry in a step the lowest env index
+ * (local, i) wins and the others' updates are dropped. With n = 1 or without collisions this
+ * is the reference. The handle owns one 4-byte claim word per entry for this.
+ *
+ * Draws: key (seed, env_id_base + i), the t word the caller's vector-step number t.
+ *   slot 20: word 0 the explore uniform of next_action, word 1 its sample_action word,
+ *            word 2 the explore uniform of a fresh env's first choice, word 3 its sample word;
+ *   slot 21: words 0, 1 the restart's origin and dest, read as se_reset reads its two words;
+ *   attempt j of _try_action (j = 0 the pending action): slot 32 + 2j word 0 the
+ *   sample_action word (j >= 1), words 1-3 u_fuel, u_gate, u_type; slot 33 + 2j three beta
+ *   uniforms and the new destination (a partial loss or an arrival), as se_rollout reads its
+ *   two blocks. */
+#define SE_SARSA_OK 0             /* a step counted; the table was updated (learn != 0) */
+#define SE_SARSA_CUT 1            /* max_attempts attempts raised (the reference keeps trying) */
+#define SE_SARSA_RAISED 2         /* a sample_action raised: the reference's train dies there */
+#define SE_SARSA_NEVER_RETURNS 3  /* a sample_action never returns (no other port) */
+typedef struct se_sarsa_state {   /* caller-owned device SoA, n entries each */
+    int32_t* type;                /* the pending action (se_step_typed's encoding) */
+    int32_t* a;
+    int32_t* b;
+    uint8_t* fresh;               /* 1: choose the pending action first (set it after a reset) */
+    int32_t* ep_len;              /* counted steps of the running episode */
+    double* ep_return;            /* their rewards summed in f64 in order */
+} se_sarsa_state;
+typedef struct se_sarsa se_sarsa;
+/* Fixes the layout for the env's world. P = 0 is refused; SE_EINVAL with the needed byte count
+ * in se_last_error() when the table and the claim words (12 bytes per entry) exceed
+ * max_table_bytes. After se_set_ports every call but _layout and _destroy returns SE_ESTATE.
+ * Destroy the handle before its env. */
+int se_sarsa_create(se_sarsa** out, se_env* env, int64_t max_table_bytes);
+int se_sarsa_layout(const se_sarsa* s, int64_t* rows, int32_t* A, int32_t* cmax);
+/* q: rows * A doubles on the env's device. The struct is copied; the buffers stay the caller's. */
+int se_sarsa_bind(se_sarsa* s, double* q, const se_sarsa_state* st);
+/* One vector step, asynchronous on the stream. learn = 0 writes no table entry (with
+ * epsilon = 0: test_policy's greedy evaluation). Outputs (device, n entries): reward, the
+ * counted step's f64 reward (0 where status != OK); ended, 1 where the episode restarted;
+ * status, SE_SARSA_*; fin_return / fin_len, the finished episode's return and length where
+ * ended. max_attempts in 1..64. The env's step counter advances by one. n = 0: a no-op. */
+int se_sarsa_step(se_sarsa* s, double lr, double gamma, double epsilon, int32_t learn, int32_t max_steps,
+                  int32_t max_attempts, uint32_t t, double* reward, uint8_t* ended, int32_t* status,
+                  double* fin_return, int32_t* fin_len, void* stream);
+/* choose_action alone from every env's current state, with slot 20's words 2 and 3; type < 0
+ * (SE_SAMPLE_*) where its sample_action raises. Nothing is modified. */
+int se_sarsa_choose(se_sarsa* s, double epsilon, uint32_t t, int32_t* type, int32_t* a, int32_t* b,
+                    void* stream);
+int se_sarsa_destroy(se_sarsa* s);
+
 /* DQN policy step fused on the GPU (agents/dqn.py): DQNNetwork 6+4P -> 128 -> 128 -> A
  * (A = 4+P+250, :21-33) evaluated with bf16 MFMA and f32 accumulation on the
  * observation preprocess_state builds (utils/preprocessing.py:25-62; its constant port

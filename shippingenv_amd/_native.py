@@ -31,6 +31,9 @@ ROLL_DONE, ROLL_MAX_STEPS, ROLL_RAISED, ROLL_ATTEMPTS, ROLL_BAD_SRC = 0, 1, 2, 3
 # se_mcts_choose statuses
 MCTS_OK, MCTS_CUT, MCTS_RAISED, MCTS_NEVER_RETURNS = 0, 1, 2, 3
 MCTS_MAX_SIMULATIONS = 256
+# se_sarsa_step statuses
+SARSA_OK, SARSA_CUT, SARSA_RAISED, SARSA_NEVER_RETURNS = 0, 1, 2, 3
+SARSA_MAX_ATTEMPTS = 64
 
 # se_server_call ops
 SERVER_STEP, SERVER_RESET_TO = 1, 2
@@ -39,7 +42,9 @@ SERVER_STEP, SERVER_RESET_TO = 1, 2
 EXPORTS = (
     "se_create", "se_set_ports", "se_bind", "se_reset", "se_reset_to", "se_step", "se_step_seq", "se_step_seq_mark",
     "se_step_typed", "se_step_replay", "se_step_agent_replay", "se_observe", "se_valid_mask", "se_gen_actions",
-    "se_sample_actions", "se_rollout", "se_mcts_create", "se_mcts_choose", "se_mcts_destroy", "se_qnet_create", "se_qnet_set_weights", "se_policy", "se_policy_f32",
+    "se_sample_actions", "se_rollout", "se_mcts_create", "se_mcts_choose", "se_mcts_destroy",
+    "se_sarsa_create", "se_sarsa_layout", "se_sarsa_bind", "se_sarsa_step", "se_sarsa_choose", "se_sarsa_destroy",
+    "se_qnet_create", "se_qnet_set_weights", "se_policy", "se_policy_f32",
     "se_qnet_repack", "se_policy_record", "se_policy_record_f32",
     "se_qnet_destroy", "se_replay_create", "se_replay_begin", "se_replay_end", "se_replay_end_reset", "se_step_record",
     "se_replay_size",
@@ -67,6 +72,10 @@ class SeState(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in (
         "x", "y", "fuel", "cargo", "origin", "dest", "reward", "done", "err", "ep_return",
         "ep_start", "done_recs", "done_count", "reward64")]
+
+
+class SeSarsaState(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("type", "a", "b", "fresh", "ep_len", "ep_return")]
 
 
 class SeDoneRec(C.Structure):
@@ -99,6 +108,12 @@ def _declare(lib):
         "se_mcts_create": [C.POINTER(P), P, i32],
         "se_mcts_choose": [P, i32, C.c_double, i32, i32, i64, P, P, P, P, P, P, P],
         "se_mcts_destroy": [P],
+        "se_sarsa_create": [C.POINTER(P), P, i64],
+        "se_sarsa_layout": [P, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)],
+        "se_sarsa_bind": [P, P, C.POINTER(SeSarsaState)],
+        "se_sarsa_step": [P, C.c_double, C.c_double, C.c_double, i32, i32, i32, u32, P, P, P, P, P, P],
+        "se_sarsa_choose": [P, C.c_double, u32, P, P, P, P],
+        "se_sarsa_destroy": [P],
         "se_qnet_create": [C.POINTER(P), P],
         "se_qnet_set_weights": [P, P, P, P, P, P, P, P],
         "se_policy": [P, P, C.c_double, u32, P, i64, P],

@@ -39,6 +39,11 @@ enum Slot : uint32_t {
     kSlotReset3 = 17,
     kSlotMcts = 18,          // MCTS tree step d, per simulation: untried-action choice, u_fuel, u_gate, u_type
     kSlotMctsB = 19,         // MCTS tree step d (partial loss / arrival): 3 beta uniforms, dest
+    kSlotSarsa = 20,         // se_sarsa_step, per env, t = the vector step: explore uniform and sample word of
+                             // next_action (words 0, 1) and of a fresh env's first choice (words 2, 3)
+    kSlotSarsaReset = 21,    // se_sarsa_step's restart: words 0 origin, 1 dest (as kSlotExplicitReset)
+    kSlotSarsaTry = 32,      // _try_action attempt j at 32 + 2j: sample word (j >= 1), u_fuel, u_gate, u_type;
+                             // 33 + 2j (partial loss / arrival): 3 beta uniforms, dest; j < 64, up to slot 159
 };
 
 // RESET_r slot of the r-th auto-reset env of a quad

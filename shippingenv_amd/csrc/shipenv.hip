@@ -90,6 +90,7 @@ struct se_env {
     int world_cap = 0;  // words allocated
     uint64_t world_version = 0;  // bumped by every world upload (se_qnet folds the ports)
     int32_t cmax = 0, fmax = 0;  // largest TAKE_CARGO / TAKE_FUEL amount any port allows (se_qnet)
+    int32_t stock_cargo_max = 0;  // largest port_cargo (se_sarsa: sample_action takes up to the whole stock)
     se_state st{};
     bool bound = false;
     double* d_slab = nullptr;       // [nslab][4]
@@ -298,10 +299,11 @@ int upload_world(se_env* env, int32_t P, const int32_t* px, const int32_t* py, c
     }
     HIP_TRY(hipMemcpy(env->d_world, img.data(), (size_t)d.padded() * 4, hipMemcpyHostToDevice));
     env->dims = d;
-    env->cmax = env->fmax = 0;
+    env->cmax = env->fmax = env->stock_cargo_max = 0;
     for (int i = 0; i < P; ++i) {  // amounts 1..49 / 1..199 exist (utils/preprocessing.py:93-108)
         env->cmax = std::max(env->cmax, std::min(pc[i], 49));
         env->fmax = std::max(env->fmax, std::min(pf[i], 199));
+        env->stock_cargo_max = std::max(env->stock_cargo_max, pc[i]);
     }
     env->world_version += 1;
     env->mask_ntmpl = 1 + P;  // se_valid_mask's row templates (mask_tmpl_kernel)
@@ -922,6 +924,7 @@ int se_host_destroy(se_host* h) {
 // the fused DQN policy step (same translation unit: world image, env handle, Philox)
 #include "qpolicy.h"
 #include "mcts.h"
+#include "sarsa.h"
 #include "replay.h"
 #include "qtrain.h"
 #include "server.h"

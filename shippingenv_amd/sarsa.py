@@ -1,0 +1,208 @@
+"""VecSARSAAgent: the reference's SARSAAgent (agents/sarsa.py) for the N envs of a VecEnv.
+
+One learner owns one dense f64 Q-table in device memory; every se_sarsa_step runs the body of
+train's inner loop (:255-272) for all envs at once: _try_action on the pending action,
+choose_action on the new state, the update, and the restart of finished episodes. All envs
+read the table as the previous vector step left it; where several update one entry in a step,
+the lowest env index wins (include/shipenv.h, DESIGN.md "Tabular SARSA"). With one env, or
+without collisions, it is the reference's learner step for step.
+Nothing here falls back to the host: a missing kernel is an error.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _native as N
+from .vec import _ptr
+
+# se_sarsa_step statuses (include/shipenv.h SE_SARSA_*)
+OK, CUT, RAISED, NEVER_RETURNS = N.SARSA_OK, N.SARSA_CUT, N.SARSA_RAISED, N.SARSA_NEVER_RETURNS
+
+MOVE, SELECT, TAKE_FUEL, TAKE_CARGO = 1, 2, 3, 4
+MOVES = ((0, -1), (0, 1), (-1, 0), (1, 0))  # _get_possible_actions' order (:105-110)
+# fuel class -> (cargo_bucket, fuel_bucket) of discretize_state, both read from the fuel
+BUCKETS = ((0, 0), (1, 0), (2, 1), (3, 1), (4, 2), (4, 3), (4, 4))
+
+
+class VecSARSAAgent:
+    """SARSAAgent(env, learning_rate, discount_factor, epsilon, epsilon_min, epsilon_decay) with
+    the reference's defaults (utils/constants.py:40-46). max_steps restarts an episode after
+    that many counted steps (ours: a greedy policy can repeat a legal SELECT forever; 0: never);
+    max_attempts (1..64) bounds _try_action's unbounded retry, a step it cuts has status CUT.
+    max_table_bytes refuses a table (with its claim words, 12 bytes per entry) beyond it.
+
+    The envs must have been reset (env.reset()) or loaded before the first step; every env starts
+    fresh, that is, its first step chooses its action first. q is the table, a torch f64 tensor
+    [rows, A] in the layout of include/shipenv.h; t, the vector-step number, selects the draws."""
+
+    def __init__(self, env, learning_rate=0.1, discount_factor=0.9, epsilon=1.0, epsilon_min=0.0001,
+                 epsilon_decay=0.999, max_steps=1000, max_attempts=8, max_table_bytes=None):
+        self.env = env
+        self.lr, self.gamma = float(learning_rate), float(discount_factor)
+        self.epsilon, self.epsilon_min, self.epsilon_decay = float(epsilon), float(epsilon_min), float(epsilon_decay)
+        self.max_steps, self.max_attempts = int(max_steps), int(max_attempts)
+        self.t = 0
+        self._carry = 0  # finished episodes not yet paid for with a decay (train)
+        self._h = C.c_void_p()
+        limit = (1 << 63) - 1 if max_table_bytes is None else int(max_table_bytes)
+        with torch.cuda.device(env.device):
+            N.check(N.lib().se_sarsa_create(C.byref(self._h), env._h, limit))
+        rows, A, cmax = C.c_int64(), C.c_int32(), C.c_int32()
+        N.check(N.lib().se_sarsa_layout(self._h, C.byref(rows), C.byref(A), C.byref(cmax)))
+        self.rows, self.A, self.cmax = rows.value, A.value, cmax.value
+        dev, n = env.device, env.n
+        self.q = torch.zeros((self.rows, self.A), dtype=torch.float64, device=dev)
+        self.type, self.a, self.b = (torch.zeros(n, dtype=torch.int32, device=dev) for _ in range(3))
+        self.fresh = torch.ones(n, dtype=torch.uint8, device=dev)
+        self.ep_len = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.ep_return = torch.zeros(n, dtype=torch.float64, device=dev)
+        self.reward = torch.zeros(n, dtype=torch.float64, device=dev)
+        self.ended = torch.zeros(n, dtype=torch.uint8, device=dev)
+        self.status = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.fin_return = torch.zeros(n, dtype=torch.float64, device=dev)
+        self.fin_len = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._bind()
+
+    def _bind(self):
+        self._state = N.SeSarsaState(*[t.data_ptr() for t in (self.type, self.a, self.b, self.fresh, self.ep_len,
+                                                              self.ep_return)])
+        N.check(N.lib().se_sarsa_bind(self._h, _ptr(self.q), C.byref(self._state)))
+
+    # ------------------------------------------------------------------ stepping
+    def step(self, learn=True, epsilon=None):
+        """One vector step -> (reward f64, ended u8, status i32) device tensors, reused by the
+        next call; fin_return / fin_len hold the finished episodes' totals where ended."""
+        eps = self.epsilon if epsilon is None else float(epsilon)
+        N.check(N.lib().se_sarsa_step(self._h, self.lr, self.gamma, eps, 1 if learn else 0, self.max_steps,
+                                      self.max_attempts, self.t & 0xFFFFFFFF, _ptr(self.reward), _ptr(self.ended),
+                                      _ptr(self.status), _ptr(self.fin_return), _ptr(self.fin_len),
+                                      self.env._stream()))
+        self.t += 1
+        return self.reward, self.ended, self.status
+
+    def choose_action(self, epsilon=None):
+        """choose_action from every env's current state -> (type, a, b) int32 device tensors, the
+        typed actions of step_typed; type < 0 where its sample_action raises. Draws the words a
+        fresh env's first choice would at vector step t; nothing is modified."""
+        eps = self.epsilon if epsilon is None else float(epsilon)
+        out = tuple(torch.zeros(self.env.n, dtype=torch.int32, device=self.env.device) for _ in range(3))
+        N.check(N.lib().se_sarsa_choose(self._h, eps, self.t & 0xFFFFFFFF, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                        self.env._stream()))
+        return out
+
+    def decay_epsilon(self):
+        self.epsilon = max(self.epsilon_min, self.epsilon * self.epsilon_decay)  # :199
+
+    def restart(self):
+        """Reset every env and mark it fresh (the start of train or test_policy)."""
+        self.env.reset()
+        self.fresh.fill_(1)
+        self.ep_len.zero_()
+        self.ep_return.zero_()
+
+    def train(self, steps, sync_every=64):
+        """`steps` learning vector steps -> (episodes finished, the sum of their returns).
+
+        The reference decays epsilon once per episode of its one env. Here n envs run their
+        episodes side by side, so epsilon decays once per n finished episodes, counted from
+        `ended` every sync_every steps (one host synchronisation each) with the remainder
+        carried: each env's episodes see the reference's schedule on average. This pacing is
+        ours; the reference has no counterpart for it."""
+        n = max(self.env.n, 1)
+        count = torch.zeros((), dtype=torch.int64, device=self.env.device)
+        total = torch.zeros((), dtype=torch.float64, device=self.env.device)
+        episodes, ret, done_steps = 0, 0.0, 0
+        while done_steps < steps:
+            k = min(int(sync_every), steps - done_steps)
+            count.zero_()
+            total.zero_()
+            for _ in range(k):
+                _, ended, _ = self.step(learn=True)
+                count += ended.sum()
+                total += self.fin_return.sum()  # 0 where the episode goes on
+            done_steps += k
+            c = int(count.item())
+            episodes += c
+            ret += float(total.item())
+            self._carry += c
+            while self._carry >= n:
+                self._carry -= n
+                self.decay_epsilon()
+        return episodes, ret
+
+    def test_policy(self, steps):
+        """Greedy evaluation (test_policy :315-356: deterministic choices, no update) for `steps`
+        vector steps from fresh resets -> {start port: mean return of the episodes that finished}.
+        The learner's step number t advances; the table does not change."""
+        env = self.env
+        self.restart()
+        P = env.P
+        sums = torch.zeros(P, dtype=torch.float64, device=env.device)
+        cnts = torch.zeros(P, dtype=torch.float64, device=env.device)
+        start = env.origin.to(torch.int64).clone()
+        for _ in range(int(steps)):
+            _, ended, _ = self.step(learn=False, epsilon=0.0)
+            fin = ended != 0
+            idx = start.clamp(max=P - 1)
+            sums.index_add_(0, idx, self.fin_return)  # 0 where the episode goes on
+            cnts.index_add_(0, idx, fin.to(torch.float64))
+            start = torch.where(fin, env.origin.to(torch.int64), start)
+        s, c = sums.cpu().tolist(), cnts.cpu().tolist()
+        self.restart()
+        return {p: s[p] / c[p] for p in range(P) if c[p] > 0}
+
+    # ------------------------------------------------------------------ the table
+    def entry_key(self, entry):
+        """Flat table entry -> the reference's dict key
+        (((x, y), cargo_bucket, fuel_bucket, prev, dest), (type, value))."""
+        P, A, W = self.env.P, self.A, self.env.W
+        row, slot = divmod(int(entry), A)
+        row, dest = divmod(row, P + 1)
+        row, origin = divmod(row, P + 1)
+        cell, cls = divmod(row, 7)
+        x, y = divmod(cell, W)
+        cb, fb = BUCKETS[cls]
+        if slot < P:
+            action = (SELECT, slot)
+        elif slot < P + 4:
+            action = (MOVE, MOVES[slot - P])
+        elif slot < P + 4 + self.cmax:
+            action = (TAKE_CARGO, slot - (P + 3))
+        else:
+            action = (TAKE_FUEL, slot - (P + 3 + self.cmax))
+        return ((x, y), cb, fb, origin - 1, dest - 1), action
+
+    def q_items(self):
+        """The non-zero entries as {reference dict key: value}."""
+        flat = self.q.view(-1)
+        idx = torch.nonzero(flat, as_tuple=False).view(-1)
+        vals = flat[idx].cpu().tolist()
+        return {self.entry_key(e): v for e, v in zip(idx.cpu().tolist(), vals)}
+
+    def save(self, path):
+        torch.save({"q": self.q.cpu(), "epsilon": self.epsilon, "lr": self.lr, "gamma": self.gamma,
+                    "layout": (self.rows, self.A, self.cmax)}, path)
+
+    def load(self, path):
+        data = torch.load(path, map_location="cpu")
+        if tuple(data["layout"]) != (self.rows, self.A, self.cmax):
+            raise ValueError(f"the saved table's layout {tuple(data['layout'])} is not this world's "
+                             f"{(self.rows, self.A, self.cmax)}")
+        self.q.copy_(data["q"])
+        self.epsilon = data.get("epsilon", self.epsilon_min)  # :402-404
+        self.lr = data.get("lr", self.lr)
+        self.gamma = data.get("gamma", self.gamma)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            torch.cuda.synchronize(self.env.device)
+            N.lib().se_sarsa_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
