@@ -504,7 +504,12 @@ int se_replay_size(se_replay* r, int64_t* size, int64_t* capacity);
  * all four are flagged or beyond size). t is read from t_dev (device u32) when non-NULL, so
  * the launch can be captured in a graph with a device-side update counter. Outputs
  * (device): obs and next_obs [batch][6+4P] f32 rows, actions int64, rewards, dones
- * (1.0 / 0.0) and weights (1.0 / 0.0) f32 [batch]. */
+ * (1.0 / 0.0) and weights (1.0 / 0.0) f32 [batch]. A weight-0 row is written as zeros
+ * throughout: both observation rows (the port block included), the action, the reward and
+ * done. size == 0 and batch > size are valid: the rows that find no transition come out at
+ * weight 0, and rows past `batch` are not written. Sampling between se_replay_begin (or
+ * se_policy_record*) and its se_replay_end* / se_step_record is unsupported: the slots of the
+ * pass in flight hold a new s beside an old s' (se_qtrain_step_replay refuses it). */
 int se_replay_sample(se_replay* r, int64_t batch, const uint32_t* t_dev, uint32_t t, float* obs,
                      float* next_obs, int64_t* actions, float* rewards, float* dones, float* weights,
                      void* stream);
