@@ -65,6 +65,7 @@ extern "C" {
 #define SE_NONE 255             /* origin/dest "None" in the u8 index fields */
 #define SE_MAX_PORTS 254
 #define SE_MAX_SIDE 256         /* H, W <= 256 (positions are u8) */
+#define SE_MAX_CARGO 715827882  /* (2^31 - 1) / 3: |cargo| and |cargo + amount| stay within it (se_state.cargo) */
 
 typedef struct se_env se_env;
 
@@ -85,7 +86,13 @@ typedef struct se_state {
     uint8_t* x;         /* ship_position[0], row of np_game      (environment.py:37,:241,:297) */
     uint8_t* y;         /* ship_position[1], column of np_game */
     double* fuel;       /* self.fuel, f64 like the reference (int 200 - sum of np.float64)  :39 */
-    int32_t* cargo;     /* self.cargo                                                      :38 */
+    int32_t* cargo;     /* self.cargo                                                      :38
+                           Contract: cargo, and cargo + amount of a TAKE_CARGO, stay within
+                           +-SE_MAX_CARGO = (2^31 - 1) / 3, the largest value for which the
+                           step's 3 * loss (and 2 * cargo at arrival) is exact in int32. The
+                           reference's unbounded ints are matched only inside that range;
+                           beyond it the int arithmetic wraps (shipping.Environment raises
+                           OverflowError instead). Negative cargo is inside the contract. */
     uint8_t* origin;    /* self.origin_port_index, SE_NONE = None                          :40 */
     uint8_t* dest;      /* self.destination_port_index, SE_NONE = None                     :41 */
     float* reward;      /* step() reward, the reference's f64 value rounded once to f32    :376 */

@@ -5,7 +5,11 @@
  *
  * Parity: pinned. The replay mode reproduces every record of
  * tests/golden/{tape,states}_seed*.npz (generated from the reference itself by
- * tests/golden/make_golden.py) bit for bit; tests/test_oracle_golden.py checks it.
+ * tests/golden/make_golden.py) bit for bit; tests/test_oracle_golden.py checks it. At the edges
+ * of the arguments and variates (tests/golden/step_edges.npz: maps of side 1 to 256, moves up to
+ * +-2^31, negative cargo, every variate on its comparison boundary) tests/test_step_edges_cpu.py
+ * does. Cargo is int32 like the kernels': the reference's unbounded ints are matched while
+ * |cargo| and |cargo + amount| stay within (2^31 - 1) / 3 (include/shipenv.h, SE_MAX_CARGO).
  * The Philox mode is the production RNG contract, which the HIP
  * kernel must match bit for bit; its distributional equivalence to the
  * reference's MT19937 draws is argued in DESIGN.md.

@@ -16,6 +16,7 @@ ABI_VERSION = 2  # include/shipenv.h SHIPENV_ABI_VERSION
 
 SE_FLAG_AUTO_RESET = 1
 SE_NONE = 255
+SE_MAX_CARGO = (2 ** 31 - 1) // 3  # include/shipenv.h: |cargo| and |cargo + amount| stay within it
 
 # per-env error classes (include/shipenv.h SE_ERR_*)
 ERR_OK, ERR_OOB, ERR_SAME_PORT, ERR_PORT_RANGE, ERR_NOT_AT_PORT = 0, 1, 2, 3, 4

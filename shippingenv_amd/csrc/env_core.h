@@ -73,7 +73,8 @@ struct Pending {
 // * 2^32) is the same test on u = w * 2^-32. Production skips the cargo-0 case (a
 // firing gate then loses nothing, :180-181); replay keeps it because the reference
 // still draws the loss type there (:177) and replay tracks every draw. From cargo
-// 50 on the gate always fires (random() < 1 <= cargo/50).
+// 50 on the gate always fires (random() < 1 <= cargo/50); below 0 it never does
+// (cargo/50 < 0 <= random()), in replay as in production.
 // u_fuel: replay, the tape's f64 uniform; production, the Philox word w as a double
 // (u = w * 2^-32), so 0.2 * u is one product with 0.2 * 2^-32: scaling by a power of
 // two is exact, so fl(w * fl(0.2) * 2^-32) == fl(fl(0.2) * u) bit for bit.
@@ -134,7 +135,9 @@ __host__ __device__ __forceinline__ Pending env_begin(const LdsWorld& w, Ship& s
     bool fires;
     if constexpr (kReplay) {
         const double lk = w.likelihood(ci);
-        fires = (s.cargo >= 50) | (u_gate <= lk);
+        // cargo < 0: random() <= cargo / 50 is false for every draw (u_gate 0.0 included),
+        // and ci = 0 above stands for cargo 0 only
+        fires = (s.cargo >= 50) | ((s.cargo >= 0) & (u_gate <= lk));
     } else {
         const uint32_t thr = w.gate_thr[ci];
         fires = (s.cargo >= 50) | ((s.cargo > 0) & (gw <= thr));

@@ -308,7 +308,8 @@ __device__ __forceinline__ void step_group_agent(const StepArgs& A, const LdsWor
         if constexpr (kReplay) {
             const double ug = tg[j];
             const int ci = ((cg[j] > 0) & (cg[j] < 50)) ? cg[j] : 0;
-            fires = do_move[j] & ((cg[j] >= 50) | (ug <= w.likelihood(ci)));
+            // cargo < 0 never fires (env_begin): ci = 0 stands for cargo 0 only
+            fires = do_move[j] & ((cg[j] >= 50) | ((cg[j] >= 0) & (ug <= w.likelihood(ci))));
             need |= (uint32_t)(do_move[j] & ((tu[j] != tu[j]) | (ug != ug))) << j;
         } else {
             const uint32_t thr = w.gate_thr[min(max(cg[j], 0), 50)];

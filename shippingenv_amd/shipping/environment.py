@@ -315,6 +315,9 @@ class Environment:
                 cell = (x + a, y + b)
         stepper = self._world(cell)
         tape = [math.nan, math.nan, math.nan, math.nan, -1]
+        cargo = int(self.cargo)
+        if abs(cargo) > N.SE_MAX_CARGO or (act_type == ActionType.TAKE_CARGO and abs(cargo + a) > N.SE_MAX_CARGO):
+            return self._run_wide(stepper, x, y, cargo, act_type, a, b, tape)
         ahead = False
         if act_type == ActionType.MOVE_SHIP and self.destination_port_index is not None:
             if cell is not None:
@@ -345,6 +348,22 @@ class Environment:
                 raise RuntimeError("step kernel asked for a variate the protocol cannot supply")
         if ahead and not (res.used & N.USED_FUEL_GATE):
             raise RuntimeError("the step kernel raised a move the host expected to draw for")
+        return res
+
+    def _run_wide(self, stepper, x, y, cargo, act_type, a, b, tape):
+        """A step whose cargo is outside the stepper's int32 contract (include/shipenv.h,
+        SE_MAX_CARGO), where the reference computes on in unbounded ints. No error depends on
+        the cargo, so the step runs once with cargo 0 and no variates: an error it reports is
+        the reference's own; SELECT_PORT and TAKE_FUEL never touch the cargo and go through;
+        a MOVE or TAKE_CARGO that would succeed raises OverflowError before any draw, and
+        nothing has changed."""
+        res = stepper.step(x, y, float(self.fuel), 0, self.origin_port_index, self.destination_port_index,
+                           act_type, a, b, tape)
+        if res.err == N.ERR_OK and act_type in (ActionType.SELECT_PORT, ActionType.TAKE_FUEL):
+            res.cargo = cargo
+            return res
+        if res.err in (N.ERR_OK, N.ERR_NEED_DRAW):
+            raise OverflowError(f"cargo {cargo} is beyond the step's int32 range (+-{N.SE_MAX_CARGO})")
         return res
 
     def step(self, action):

@@ -1,0 +1,184 @@
+"""The step-edge fixture (tests/golden/step_edges.npz, recorded from the reference by
+tests/golden/make_step_edge_golden.py) as the tests read it: the worlds, one batch of records
+per world, their tapes, the agent-expressible subset, and a scripted ``random`` for the drop-in.
+Shared by test_step_edges_cpu.py and test_gpu_step_edges.py. numpy only.
+
+Records with beyond_contract = 1 hold a cargo outside the int32 contract of include/shipenv.h
+(|cargo|, |cargo + amount| <= (2^31 - 1) / 3). They are the only records the tests skip, and by
+that column alone.
+"""
+import functools
+import json
+import os
+
+import numpy as np
+
+from conftest import GOLDEN, load_golden
+
+FIELDS = ("x", "y", "fuel", "cargo", "origin", "dest")
+BOUND = (2 ** 31 - 1) // 3
+USED_FUEL_GATE, USED_LOSS_TYPE, USED_BETA, USED_ARRIVE, USED_MOVED = 1, 2, 4, 8, 16
+RESET_SLOTS = (4, 10, 16, 17)  # DESIGN.md "RNG contract": the RESET_r blocks of a quad
+
+# every edge class the fixture must hit (step_edges_meta.json "counts")
+_EDGE = (-2 ** 31, -257, -256, -255, -1, 0, 1, 255, 256, 257, 2 ** 31 - 1)
+_CARGO = (-7, -1, 0, 1, 24, 25, 49, 50, 51, 2 ** 21 - 1, 2 ** 21, 2 ** 21 + 1, 2 ** 24 + 1, BOUND - 1, BOUND, -BOUND)
+_AMOUNT = ("min", "-1", "0", "1", "stock", "stock+1", "max")
+REQUIRED_CLASSES = (
+    [f"move_component_{v}" for v in _EDGE]
+    + ["move_zero_on_port", "move_zero_off_port", "move_zero_fuel_edges", "move_beyond_int32_clamped",
+       "long_jump_onto_destination", "long_jump_onto_other_port", "long_jump_onto_ground",
+       "long_jump_onto_water", "move_mid_range_jump", "move_moved", "move_blocked_by_ground",
+       "arrival", "arrival_while_blocked", "fuel_out", "gate_fired", "beta_drawn"]
+    + [f"select_{v}" for v in ("min", "-1", "0", "origin", "P-1", "P", "255", "256", "max")]
+    + [f"take_{k}_{v}" for k in ("cargo", "fuel") for v in _AMOUNT + ("at_port", "off_port", "shared_cell",
+                                                                      "stock_of_second_port")]
+    + ["take_cargo_onto_bound", "take_cargo_from_negative_bound"]
+    + [f"category_{v}" for v in (-2 ** 31, -1, 0, 5, 2 ** 31 - 1)]
+    + ["world_no_ports", "dest_none_move_in_range", "dest_none_move_out_of_range", "dest_none_other_action"]
+    + [f"world_side_{s}" for s in (1, 2, 3, 100, 256)]
+    + [f"err_{e}" for e in range(9)]
+    + [f"cargo_{c}" for c in _CARGO] + ["negative_cargo_gate_0.0", "beyond_contract"]
+    + [f"fuel_{v}" for v in ("-0.0", "0.0", "5e-324", "eq_cost", "cost_minus_ulp", "cost_plus_ulp", "int_200",
+                             "1e300", "inf")]
+    + [f"u_fuel_{v}" for v in ("0", "2^-53", "1-2^-53")]
+    + ["u_gate_0.0"] + [f"u_gate_{p}{c}/50" for c in (1, 25, 49) for p in ("prev_", "", "next_")]
+    + [f"u_type_{v}" for v in ("0.0", "prev_0.1", "0.1", "next_0.1", "prev_0.9", "0.9", "next_0.9")]
+    + [f"beta_{v}" for v in ("0.0", "2^-30", "1/3", "1-2^-53", "product_ulp_below_integer",
+                             "product_on_integer", "product_ulp_above_integer")]
+)
+
+
+@functools.lru_cache(maxsize=None)
+def fixture():
+    z = load_golden(os.path.join(GOLDEN, "step_edges.npz"))
+    for v in z.values():
+        v.setflags(write=False)
+    return z
+
+
+def meta():
+    with open(os.path.join(GOLDEN, "step_edges_meta.json")) as f:
+        return json.load(f)
+
+
+def n_worlds():
+    return meta()["worlds"]
+
+
+def world(w):
+    """(water, port_x, port_y, port_fuel, port_cargo) of world w."""
+    z = fixture()
+    return tuple(z[f"w{w}_{k}"] for k in ("water", "port_x", "port_y", "port_fuel", "port_cargo"))
+
+
+def records(w, extra=None):
+    """Indices of world w's records inside the contract (and where `extra`, a bool column)."""
+    z = fixture()
+    m = (z["world"] == w) & (z["beyond_contract"] == 0)
+    if extra is not None:
+        m &= extra
+    return np.nonzero(m)[0]
+
+
+def agent_expressible():
+    """Records whose typed action the reference's decode produces from an agent index (unit
+    moves, a port in range, amounts below 50 / 200): agent_idx is that index."""
+    z = fixture()
+    return z["agent_idx"] >= 0
+
+
+def tape_of(dtype, sel):
+    z = fixture()
+    tape = np.zeros(len(sel), dtype)
+    for f in ("u_fuel", "u_gate", "u_type", "beta", "arrive_dest"):
+        tape[f] = z[f][sel]
+    return tape
+
+
+def pre_state(sel, u8_none=False):
+    """Pre-state columns; origin / dest as -1 = None, or 255 with u8_none (the device form)."""
+    z = fixture()
+    out = {}
+    for f in FIELDS:
+        v = z["pre_" + f][sel]
+        if f in ("origin", "dest") and u8_none:
+            v = np.where(v < 0, 255, v)
+        out[f] = v.astype(np.int32) if f == "cargo" else v
+    return out
+
+
+def want_post(sel):
+    z = fixture()
+    return {f: z["post_" + f][sel] for f in FIELDS}
+
+
+def assert_post(got, sel, what):
+    """got: dict of post-state arrays (origin / dest with -1 = None) against the fixture, fuel by bits."""
+    want = want_post(sel)
+    for f in FIELDS:
+        if f == "fuel":
+            np.testing.assert_array_equal(np.asarray(got[f], np.float64).view(np.int64),
+                                          want[f].view(np.int64), err_msg=f"{what}: fuel bits")
+        else:
+            np.testing.assert_array_equal(np.asarray(got[f]).astype(np.int64), want[f], err_msg=f"{what}: {f}")
+
+
+def n_randint(i):
+    """How many randint calls record i's arrival redraw made (all but the last returned the new origin)."""
+    z = fixture()
+    k = int(z["draw_kinds"][i])
+    return int(z["n_draws"][i]) - (2 * (k & 1) + ((k >> 1) & 1) + ((k >> 2) & 1))
+
+
+class Scripted:
+    """Stands in for the ``random`` module under the drop-in: hands out record i's variates in the
+    order the drop-in asks for them (random() for the fuel uniform, the gate and the loss type) and
+    counts the calls. A draw the reference did not make is a NaN / missing here and fails the test."""
+
+    def __init__(self):
+        self.calls = 0
+
+    def load(self, i):
+        z = fixture()
+        self.calls = 0
+        self._random = [float(z[f][i]) for f in ("u_fuel", "u_gate", "u_type")]
+        self._beta = float(z["beta"][i])
+        k = n_randint(i)
+        self._randint = [int(z["pre_dest"][i])] * (k - 1) + [int(z["arrive_dest"][i])] if k else []
+
+    def random(self):
+        self.calls += 1
+        v = self._random.pop(0)
+        assert v == v, "the reference did not draw this random()"
+        return v
+
+    def betavariate(self, a, b):
+        self.calls += 1
+        assert (a, b) == (2, 2) and self._beta == self._beta
+        return self._beta
+
+    def randint(self, a, b):
+        self.calls += 1
+        v = self._randint.pop(0)
+        assert a <= v <= b
+        return v
+
+
+def philox_autoreset(O, oworld, st, seed, t):
+    """The auto-reset half of a step on an oracle state whose step (typed or not) has just run:
+    the envs with done set restart from RESET_r blocks exactly as orc_step_batch_autoreset does
+    it (the r-th finished env of quad k at counter (k, t, RESET_r): word 0 the origin, word 1 the
+    destination among the others)."""
+    key = [seed & 0xFFFFFFFF, seed >> 32]
+    rank = {}
+    for i in np.nonzero(st.done)[0]:
+        q = int(i) >> 2
+        r = rank.get(q, 0)
+        rank[q] = r + 1
+        o = O.philox([q & 0xFFFFFFFF, q >> 32, t, RESET_SLOTS[r]], key)
+        origin = (int(o[0]) * oworld.P) >> 32
+        k = (int(o[1]) * (oworld.P - 1)) >> 32
+        st.origin[i], st.dest[i] = origin, k + (k >= origin)
+        st.cargo[i], st.fuel[i] = 0, 200.0
+        st.x[i], st.y[i] = oworld.px[origin], oworld.py[origin]

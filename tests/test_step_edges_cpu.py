@@ -1,0 +1,226 @@
+"""The typed step at the edges of its arguments and variates, without a GPU: the C oracle in
+replay mode, the host build of the step kernels' per-env code (se_host_step_replay) and the
+drop-in Environment on it, each against what the reference itself did on every record of
+tests/golden/step_edges.npz (tests/golden/make_step_edge_golden.py: moves up to +-2^31 on maps
+of side 1 to 256, cargo from negative to the int32 contract's bound, fuel from -0.0 to inf, and
+every variate on its comparison boundary). This is what makes the oracle trustworthy as the
+reference of test_gpu_step_edges.py on this domain."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+import step_edge_support as S
+from conftest import GOLDEN
+
+WORLDS = range(S.n_worlds())
+
+
+def test_fixture_covers_every_edge_class():
+    counts = S.meta()["counts"]
+    missing = [c for c in S.REQUIRED_CLASSES if counts.get(c, 0) <= 0]
+    assert not missing, missing
+    z = S.fixture()
+    n = len(z["world"])
+    assert S.meta()["records"] == n > 10_000
+    # what can be recounted from the columns agrees with the counts block
+    for e in range(9):
+        assert int((z["err"] == e).sum()) > 0
+    assert set(np.unique(z["world"]).tolist()) == set(WORLDS)
+    for side, w in zip((1, 2, 3, 100, 256, 3), WORLDS):
+        assert S.world(w)[0].shape == (side, side)
+    assert len(S.world(5)[1]) == 0  # P = 0
+    for k in (1, 2, 4, 8, 16):
+        assert int(((z["used"] & k) != 0).sum()) > 0
+
+
+def test_skipped_share_stays_below_one_percent():
+    """beyond_contract marks exactly the records whose cargo leaves +-(2^31 - 1) / 3, and the tests
+    skip by that column only: under 1 % of the records."""
+    z = S.fixture()
+    beyond = (np.abs(z["pre_cargo"]) > S.BOUND) | (np.abs(z["post_cargo"]) > S.BOUND)
+    np.testing.assert_array_equal(z["beyond_contract"] != 0, beyond)
+    assert 0 < beyond.sum() < 0.01 * len(beyond)
+    assert S.meta()["beyond_contract"] == int(beyond.sum()) and S.meta()["bound"] == S.BOUND
+    # the largest cargo inside the contract sits exactly on the bound, reached by a take too
+    inside = ~beyond
+    assert z["pre_cargo"][inside].max() == S.BOUND == z["post_cargo"][inside & (z["act_type"] == 4)].max()
+    assert z["pre_cargo"][inside].min() == -S.BOUND
+
+
+@pytest.mark.parametrize("w", WORLDS)
+def test_oracle_replays_reference_edges(oracle_mod, w):
+    """State, fuel bits, f64 reward bits, done, err and the draws made, on every record."""
+    O = oracle_mod
+    z = S.fixture()
+    sel = S.records(w)
+    assert len(sel)
+    st = O.OracleState(len(sel))
+    for f, v in S.pre_state(sel).items():
+        getattr(st, f)[:] = v
+    tape = S.tape_of(O.TAPE_DTYPE, sel)
+    O.step(O.OracleWorld(*S.world(w)), st, act_type=z["act_type"][sel], act_a=z["act_a"][sel],
+           act_b=z["act_b"][sel], tape=tape)
+    S.assert_post({f: getattr(st, f) for f in S.FIELDS}, sel, f"oracle world {w}")
+    np.testing.assert_array_equal(st.reward.view(np.int64), z["reward"][sel].view(np.int64))
+    np.testing.assert_array_equal(st.done, z["done"][sel])
+    np.testing.assert_array_equal(st.err, z["err"][sel])
+    np.testing.assert_array_equal(tape["used"], z["used"][sel])
+
+
+def _host(w, sel):
+    from shippingenv_amd.shipping._host import host_step_replay
+    from shippingenv_amd.vec import TAPE_DTYPE
+
+    z = S.fixture()
+    return host_step_replay(*S.world(w), S.pre_state(sel, u8_none=True), z["act_type"][sel], z["act_a"][sel],
+                            z["act_b"][sel], S.tape_of(TAPE_DTYPE, sel))
+
+
+@pytest.mark.parametrize("w", WORLDS)
+def test_host_replay_matches_reference_edges(w):
+    """se_host_step_replay (the kernels' own replay_env) on every record; tape.used must equal the
+    draws the reference itself made (until now `used` was only compared kernel to host)."""
+    z = S.fixture()
+    sel = S.records(w)
+    got = _host(w, sel)
+    post = {f: (np.where(got[f] == 255, -1, got[f].astype(np.int32)) if f in ("origin", "dest") else got[f])
+            for f in S.FIELDS}
+    S.assert_post(post, sel, f"host world {w}")
+    np.testing.assert_array_equal(got["reward64"].view(np.int64), z["reward"][sel].view(np.int64))
+    np.testing.assert_array_equal(got["reward"], z["reward"][sel].astype(np.float32))
+    np.testing.assert_array_equal(got["done"].astype(np.int32), z["done"][sel])
+    np.testing.assert_array_equal(got["err"].astype(np.int32), z["err"][sel])
+    np.testing.assert_array_equal(got["tape"]["used"], z["used"][sel])
+
+
+def test_negative_cargo_never_fires_the_gate():
+    """random() <= cargo / 50 is false for every draw when cargo < 0 (environment.py:320), a gate
+    draw of exactly 0.0 included: two draws, cargo kept, no loss type reported."""
+    z = S.fixture()
+    neg = S.records(3, (z["pre_cargo"] < 0) & (z["act_type"] == 1) & (z["err"] == 0))
+    zero = neg[z["u_gate"][neg] == 0.0]
+    assert len(zero) > 10 and len(neg) > 100
+    assert ((z["draw_kinds"][neg] & (S.USED_LOSS_TYPE | S.USED_BETA)) == 0).all()  # the reference
+    got = _host(3, neg)
+    assert ((got["tape"]["used"] & (S.USED_LOSS_TYPE | S.USED_BETA)) == 0).all()
+    stay = (z["draw_kinds"][neg] & S.USED_ARRIVE) == 0
+    np.testing.assert_array_equal(got["cargo"][stay], z["pre_cargo"][neg][stay])
+
+
+def test_autoreset_helper_is_the_oracles_autoreset(oracle_mod):
+    """step_edge_support.philox_autoreset (what the GPU test applies after a typed oracle step, for
+    which the oracle has no auto-reset entry point) after orc_step_batch equals
+    orc_step_batch_autoreset on agent actions, finished envs included."""
+    O = oracle_mod
+    z = S.fixture()
+    sel = S.records(3, S.agent_expressible())
+    idx = z["agent_idx"][sel]
+    world = O.OracleWorld(*S.world(3))
+    a, b = O.OracleState(len(sel)), O.OracleState(len(sel))
+    for st in (a, b):
+        for f, v in S.pre_state(sel).items():
+            getattr(st, f)[:] = v
+    O.step_autoreset(world, a, idx, seed=991, t=5)
+    O.step(world, b, actions=idx, seed=991, t=5)
+    S.philox_autoreset(O, world, b, 991, 5)
+    assert a.done.sum() > 50
+    quads = np.bincount(np.nonzero(a.done)[0] >> 2)
+    assert quads.max() >= 2  # some quad restarts more than one env: RESET_1 is drawn
+    for f in S.FIELDS:
+        np.testing.assert_array_equal(getattr(a, f), getattr(b, f), err_msg=f)
+
+
+@pytest.fixture()
+def dropin(monkeypatch):
+    """A drop-in Environment on the host stepper, holding the 100-side world, with a scripted random."""
+    from shippingenv_amd.maps import BUILTIN_MAP
+    from shippingenv_amd.shipping import Environment, environment
+
+    environment._set_stepper_factory(None)
+    monkeypatch.setenv("SHIPENV_STEPPER", "host")
+    rng = S.Scripted()
+    monkeypatch.setattr(environment, "random", rng)
+    water, px, py, pf, pc = S.world(3)
+    env = Environment(BUILTIN_MAP)
+    g = water.astype(int)
+    g[px, py] = 2  # Entity.PORT
+    env.size_game, env.np_game = (100, 100), g
+    env.port_positions = [[int(a), int(b)] for a, b in zip(px, py)]
+    env.port_fuel, env.port_cargo = [int(v) for v in pf], [int(v) for v in pc]
+    return env, rng
+
+
+def _dropin_step(env, rng, i):
+    """Record i through env.step: (exception or None, reward, done), np_game restored afterwards."""
+    z = S.fixture()
+    x, y = int(z["pre_x"][i]), int(z["pre_y"][i])
+    t, a, b = int(z["act_type"][i]), int(z["raw_a"][i]), int(z["raw_b"][i])
+    fuel = float(z["pre_fuel"][i])
+    env.ship_position = [x, y]
+    env.fuel = int(fuel) if z["pre_fuel_is_int"][i] else fuel
+    env.cargo = int(z["pre_cargo"][i])
+    env.origin_port_index = None if z["pre_origin"][i] < 0 else int(z["pre_origin"][i])
+    env.destination_port_index = None if z["pre_dest"][i] < 0 else int(z["pre_dest"][i])
+    rng.load(i)
+    cells = [(x, y)]
+    if t == 1 and 0 <= x + a < 100 and 0 <= y + b < 100:
+        cells.append((x + a, y + b))
+    saved = [env.np_game[c] for c in cells]
+    try:
+        _, reward, done, _ = env.step([t, (a, b) if t == 1 else a])
+        return None, reward, done
+    except Exception as e:  # noqa: BLE001 - exceptions are the reference's control flow
+        return e, None, None
+    finally:
+        for c, v in zip(cells, saved):
+            env.np_game[c] = v
+
+
+def test_dropin_matches_reference_edges(dropin):
+    """The drop-in on the host stepper over the 100-side world's records: the reference's exception
+    type and message, its number of draws, its Python types for reward and fuel, its values."""
+    env, rng = dropin
+    z = S.fixture()
+    with open(os.path.join(GOLDEN, "golden_meta.json")) as f:
+        errors = {v: k for k, v in json.load(f)["errors"].items()}
+    sel = S.records(3)
+    assert len(sel) > 5000
+    for i in sel:
+        exc, reward, done = _dropin_step(env, rng, i)
+        where = f"record {i}"
+        assert rng.calls == z["n_draws"][i], where
+        if z["err"][i]:
+            assert exc is not None and f"{type(exc).__name__}: {exc}" == errors[int(z["err"][i])], (where, exc)
+            continue
+        assert exc is None, (where, exc)
+        assert isinstance(reward, int) == bool(z["reward_is_int"][i]), where
+        assert isinstance(env.fuel, int) == bool(z["post_fuel_is_int"][i]), where
+        assert float(reward) == z["reward"][i] and done is bool(z["done"][i]), where
+        assert np.float64(env.fuel).view(np.int64) == z["post_fuel"][i:i + 1].view(np.int64)[0], where
+        assert (list(env.ship_position), env.cargo) == ([z["post_x"][i], z["post_y"][i]], z["post_cargo"][i]), where
+        assert (env.origin_port_index, env.destination_port_index) == tuple(
+            None if v < 0 else v for v in (z["post_origin"][i], z["post_dest"][i])), where
+
+
+def test_dropin_refuses_cargo_beyond_the_contract(dropin):
+    """Outside the int32 contract the drop-in raises the reference's own exception where the
+    reference raises, and OverflowError (no wrapped number, no draw, no change) otherwise."""
+    env, rng = dropin
+    z = S.fixture()
+    sel = np.nonzero((z["world"] == 3) & (z["beyond_contract"] != 0))[0]
+    assert len(sel) > 10
+    for i in sel:
+        exc, _, _ = _dropin_step(env, rng, i)
+        assert z["err"][i] == 0  # the fixture's beyond-contract records all succeed in the reference
+        assert isinstance(exc, OverflowError), (i, exc)
+        assert rng.calls == 0 and env.cargo == z["pre_cargo"][i]
+    # an error the reference raises first still wins: a move out of range with cargo 2^30
+    env.ship_position, env.cargo, env.fuel = [0, 0], 2 ** 30, 200
+    env.origin_port_index, env.destination_port_index = 0, 1
+    with pytest.raises(ValueError, match="Move is out of range"):
+        env.step([1, (-1, 0)])
+    with pytest.raises(OverflowError):
+        env.step([1, (1, 0)])
+    assert env.step([2, 2])[1] == 0 and env.cargo == 2 ** 30  # SELECT and TAKE_FUEL do not touch cargo
