@@ -172,6 +172,11 @@ int se_step(se_env* env, const int32_t* actions, void* stream);
  * NOT written: the buffers hold the last step's alone, as the state buffers hold only
  * the final state. The steps of a launch before its last do not compute reward, done or
  * err at all, only the state (the last step of every launch is a full one).
+ * In a fused launch's state-only steps a wave draws the cargo-loss gate's Philox block only for
+ * its lanes that carry cargo, ahead of time and into wave-private LDS (6 KiB per workgroup
+ * behind the world image and the 2 KiB table of stocks by cell code); SHIPENV_SEQ_GATE_POOL=0
+ * at se_create, or a world image that leaves no room for it under the 64 KiB of a launch,
+ * draws it for every lane every step instead. The results are the same bits.
  * SHIPENV_SEQ_FUSE=0 at se_create issues one se_step launch per step
  * instead (the same kernel code as se_step's under a trace name of its own). With
  * auto-reset the run is always a launch per step (done lists, statistics and episode

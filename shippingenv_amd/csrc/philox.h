@@ -195,6 +195,71 @@ __host__ __device__ __forceinline__ U4x2 draw2(const Key& k, const PairInv& v, u
     return U4x2{o[0], o[1]};
 }
 
+// One block of the pair by itself: draw2's arithmetic for block b alone, the three rounds it
+// shares with the other block included, from the key and the four words of the quad that the
+// block depends on: e1, PairInv's c3 and the block's hi / lo. The state-only step draws FUEL
+// this way when its GATE words come from the wave's pool (step_seq.h), and a pool refill draws
+// GATE this way for another lane's quad, whose four words (GateSeed) came through LDS. The words
+// are those of draw(k, t, slot) bit for bit (tools/philox_gate_pool_check.cpp, on the host).
+struct GateSeed {
+    uint32_t c3, hi, lo, e1;  // PairInv's c3, hi[1], lo[1] and the key's e1
+};
+
+__host__ __device__ __forceinline__ U4 draw_half(uint32_t k0, uint32_t k1, uint32_t e1, uint32_t vc3, uint32_t hi,
+                                                 uint32_t lo, uint32_t t) {
+    // rounds 1-3, the common parts (as in draw2)
+    const uint64_t q1 = (uint64_t)kPhiloxM1 * t;
+    const uint32_t n0 = xor3((uint32_t)(q1 >> 32), e1, k0);
+    k0 += kPhiloxW0;
+    k1 += kPhiloxW1;
+    const uint64_t q0 = (uint64_t)kPhiloxM0 * n0;
+    const uint32_t n2 = xor3((uint32_t)(q0 >> 32), vc3, k1);
+    const uint32_t c3 = (uint32_t)q0;
+    k1 += kPhiloxW1;
+    const uint64_t q2 = (uint64_t)kPhiloxM1 * n2;
+    uint32_t r0 = k0, r1 = k1;
+#ifdef __HIP_DEVICE_COMPILE__
+    asm volatile("" : "+s"(r0), "+s"(r1));
+#endif
+    uint32_t a0 = xor3(hi, (uint32_t)q1, r0);  // round 2's n0
+    uint32_t a1, a2, a3;
+    r0 += kPhiloxW0;
+    {   // round 3
+        const uint64_t p0 = (uint64_t)kPhiloxM0 * a0;
+        a0 = xor3((uint32_t)(q2 >> 32), lo, r0);
+        a2 = xor3((uint32_t)(p0 >> 32), c3, r1);
+        a1 = (uint32_t)q2;
+        a3 = (uint32_t)p0;
+        r0 += kPhiloxW0;
+        r1 += kPhiloxW1;
+    }
+#pragma unroll
+    for (int r = 3; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)kPhiloxM0 * a0;
+        const uint64_t p1 = (uint64_t)kPhiloxM1 * a2;
+        a0 = xor3((uint32_t)(p1 >> 32), a1, r0);
+        a2 = xor3((uint32_t)(p0 >> 32), a3, r1);
+        a1 = (uint32_t)p1;
+        a3 = (uint32_t)p0;
+        r0 += kPhiloxW0;
+        r1 += kPhiloxW1;
+    }
+    return U4{{a0, a1, a2, a3}};
+}
+
+__host__ __device__ __forceinline__ U4 draw_fuel(const Key& k, const PairInv& v, uint32_t t) {
+    return draw_half(k.k0, k.k1, k.e1, v.c3, v.hi[0], v.lo[0], t);
+}
+
+__host__ __device__ __forceinline__ GateSeed gate_seed(const Key& k, const PairInv& v) {
+    return GateSeed{v.c3, v.hi[1], v.lo[1], k.e1};
+}
+
+// the GATE block of the quad whose seed is g, at counter t, under the key (k0, k1)
+__host__ __device__ __forceinline__ U4 draw_gate_pooled(uint32_t k0, uint32_t k1, const GateSeed& g, uint32_t t) {
+    return draw_half(k0, k1, g.e1, g.c3, g.hi, g.lo, t);
+}
+
 // integer uniform on [0, m): high word of r * m (bias < m / 2^32)
 __device__ __forceinline__ int32_t uniform_int(uint32_t r, uint32_t m) {
     return (int32_t)__umulhi(r, m);

@@ -107,6 +107,7 @@ struct se_env {
     bool nt_loads = false;  // nontemporal state loads in the step kernel (step_nt_loads)
     bool seq_fuse = true;   // se_step_seq without auto-reset: one launch per run (SHIPENV_SEQ_FUSE=0: one per step)
     int32_t seq_max_steps = 1024;  // steps of one fused launch at most (seq_max_steps)
+    bool seq_gate_pool = true;  // the fused launch draws GATE through the wave's pool (SHIPENV_SEQ_GATE_POOL=0: draw2)
 };
 
 // A host-resident world (se_host_*): no device, no HIP call. It steps envs whose SoA
@@ -163,8 +164,9 @@ int grid_for(int64_t items, int cap = kMaxBlocks) {
 }
 
 // ---------------------------------------------------------------- launch-time switches
-// SHIPENV_STEP_BLOCKS, _DONE_PAD, _NT_LOADS, _SEQ_MAX_STEPS, _SEQ_FUSE and _MASK_TILED: se_create
-// resolves all six, once, into the se_env, and a launch reads no environment variable.
+// SHIPENV_STEP_BLOCKS, _DONE_PAD, _NT_LOADS, _SEQ_MAX_STEPS, _SEQ_FUSE, _SEQ_GATE_POOL and
+// _MASK_TILED: se_create resolves all seven, once, into the se_env, and a launch reads no
+// environment variable.
 
 // Workgroup cap of the step kernel: each thread then walks ceil(groups / (cap*256))
 // groups, loading the next group after storing the current one.
@@ -216,6 +218,14 @@ int32_t seq_max_steps() {
 }
 bool seq_fuse() {
     const char* v = getenv("SHIPENV_SEQ_FUSE");
+    return !v || atoi(v) != 0;
+}
+
+// SHIPENV_SEQ_GATE_POOL=0: the fused launch's state-only steps draw FUEL and GATE together every
+// step (draw2) instead of taking GATE from the wave's pool (step_seq.h): the same-library control
+// of the pool's measurements and tests. Results are the same bits either way.
+bool seq_gate_pool() {
+    const char* v = getenv("SHIPENV_SEQ_GATE_POOL");
     return !v || atoi(v) != 0;
 }
 
@@ -434,9 +444,14 @@ int launch_step_seq(se_env* env, const int32_t* act, int64_t ld, int32_t steps, 
     const StepArgs A = step_args(env, act);
     const hipStream_t s = (hipStream_t)stream;
     if (env->n >= kEnvsPerThread) {  // at least one full group (the kernel's first load assumes it)
-        const size_t lds = lds_bytes(env) + kStockByCodeBytes;  // the image, then stock_by_code's table
-        if (env->nt_loads) step_seq_kernel<true><<<env->grid, kStepBlock, lds, s>>>(A, steps, ld);
-        else step_seq_kernel<false><<<env->grid, kStepBlock, lds, s>>>(A, steps, ld);
+        // the image, then stock_by_code's table, then the waves' GATE pools. A world whose image
+        // leaves no room for the pools under the 64 KiB a launch can ask for draws directly.
+        const size_t base = lds_bytes(env) + kStockByCodeBytes;
+        const bool pool = env->seq_gate_pool && base + kGatePoolBytes <= (size_t)64 * 1024;
+        const size_t lds = base + (pool ? kGatePoolBytes : 0);
+        const auto kernel = pool ? (env->nt_loads ? step_seq_kernel<true, true> : step_seq_kernel<false, true>)
+                                 : (env->nt_loads ? step_seq_kernel<true, false> : step_seq_kernel<false, false>);
+        kernel<<<env->grid, kStepBlock, lds, s>>>(A, steps, ld);
         HIP_TRY(hipGetLastError());
     }
     if (env->n & 3) {
@@ -522,6 +537,7 @@ int se_create(se_env** out, int device, int64_t n, int64_t env_id_base, int32_t 
         env->nt_loads = step_nt_loads(env);
         env->seq_fuse = seq_fuse();
         env->seq_max_steps = seq_max_steps();
+        env->seq_gate_pool = seq_gate_pool();
         env->mask_tiled = mask_tiled();
     }
     hipError_t e = hipMalloc(&env->d_slab, (size_t)env->nslab * 4 * sizeof(double));

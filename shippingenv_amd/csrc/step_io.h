@@ -141,17 +141,18 @@ __device__ __forceinline__ void ld4_full(const T* __restrict__ p, int64_t g0, T 
 }
 
 template <typename T>
-__device__ __forceinline__ void st4_full(T* __restrict__ p, int64_t g0, const T (&v)[4]) {
+__device__ __forceinline__ void st4_full(T* __restrict__ p, int64_t g0, const T (&v)[4],
+                                         uint32_t lane = threadIdx.x) {
     if constexpr (sizeof(T) == 4) {
         uint4 w;
         w.x = __builtin_bit_cast(uint32_t, v[0]);
         w.y = __builtin_bit_cast(uint32_t, v[1]);
         w.z = __builtin_bit_cast(uint32_t, v[2]);
         w.w = __builtin_bit_cast(uint32_t, v[3]);
-        st_at(slab_of(p, g0), 16u * threadIdx.x, w);
+        st_at(slab_of(p, g0), 16u * lane, w);
     } else {
-        st_at(slab_of(p, g0), 32u * threadIdx.x, make_double2(v[0], v[1]));
-        st_at(slab_of(p, g0), 32u * threadIdx.x + 16u, make_double2(v[2], v[3]));
+        st_at(slab_of(p, g0), 32u * lane, make_double2(v[0], v[1]));
+        st_at(slab_of(p, g0), 32u * lane + 16u, make_double2(v[2], v[3]));
     }
 }
 
@@ -171,8 +172,9 @@ __device__ __forceinline__ uint32_t ld4u8_full(const uint8_t* __restrict__ p, in
                                                uint32_t lane = threadIdx.x) {
     return ld_stream<kNt>(reinterpret_cast<const uint32_t*>(slab_of(p, g0)) + lane);
 }
-__device__ __forceinline__ void st4u8_full(uint8_t* __restrict__ p, int64_t g0, uint32_t w) {
-    st_at(slab_of(p, g0), 4u * threadIdx.x, w);
+__device__ __forceinline__ void st4u8_full(uint8_t* __restrict__ p, int64_t g0, uint32_t w,
+                                           uint32_t lane = threadIdx.x) {
+    st_at(slab_of(p, g0), 4u * lane, w);
 }
 __device__ __forceinline__ uint32_t ld4u8_tail(const uint8_t* __restrict__ p, int64_t base, int64_t n) {
     uint32_t w = 0;

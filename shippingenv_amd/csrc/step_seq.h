@@ -1,6 +1,6 @@
 #pragma once
 // step_seq.h — se_step_seq's fused run of steps with the state in registers:
-// Carried, the state-only step_group_state, stock_by_code, step_seq_kernel and
+// Carried, the state-only step_group_state, stock_by_code, the GATE pool, step_seq_kernel and
 // the partial last group's step_tail_seq_kernel.
 //
 // A fragment of shipenv.hip's translation unit, included inside its anonymous
@@ -21,20 +21,29 @@
 // it is the byte the ground test read at the cell moved to), so a step makes one cell lookup per
 // env, with the table's LDS address riding in the dot product (lds_cell). The complements of the
 // action-range compares are s_not of their lane masks (with_complement). The caller draws FUEL
-// and GATE together (fb, gb: philox.h, draw2). The ranked LOSS draw is step_group_agent's, line
+// and GATE together (fb, gb: philox.h, draw2), or takes gb from its wave's GATE pool and lets
+// `late` draw FUEL (below). The ranked LOSS draw is step_group_agent's, line
 // for line: as a shared helper it compiled to another instruction order in both steps.
 // The take and the arrival test run only for a wave that needs them (two ballots per step,
 // scalar branches). Ships are mostly at sea, so most wave-steps run neither
-// (profiles/seq_guard/freq.json).
+// (profiles/seq_guard/freq.json). The result says whether the take block ran (wave-uniform): the
+// only place where an env's cargo can become positive, which the caller's GATE pool needs.
 struct Carried {
     uint32_t pos[4];  // x | y << 16
     int org[4], dst[4];
     uint32_t code[4];   // the cell code under the ship, w.cell[cell_of(pos)]
     const int2* take;   // the block's stocks by cell code (stock_by_code), the same for every env
 };
-template <bool kNt>
-__device__ __forceinline__ void step_group_state(const LdsWorld& w, const Key& qk, uint32_t t, const U4& fb,
-                                                 const U4& gb, Group<false, false, kNt>& G, Carried& U) {
+// `late` runs after the take block and may set fb: the pooled kernel draws FUEL there and pins
+// the words, which keeps the draw out of the step's last block and, as it happens, cargo and fuel
+// in their registers across the take block (drawn before the call the loop had 10 VALU more, 7
+// of them copies where the skipped take block's path joins: profiles/seq_gatepool/isa.json).
+struct NoLateDraw {
+    __device__ __forceinline__ void operator()(U4&) const {}
+};
+template <bool kNt, typename Late = NoLateDraw>
+__device__ __forceinline__ bool step_group_state(const LdsWorld& w, const Key& qk, uint32_t t, U4 fb, const U4& gb,
+                                                 Group<false, false, kNt>& G, Carried& U, Late late = Late{}) {
     const int P = w.P;
     const uint32_t lim = (uint32_t)(w.H - 1) | ((uint32_t)(w.W - 1) << 16);
     const uint32_t wh = (uint32_t)w.W | (1u << 16);
@@ -51,7 +60,8 @@ __device__ __forceinline__ void step_group_state(const LdsWorld& w, const Key& q
     bool take_any = false;
 #pragma unroll
     for (int j = 0; j < 4; ++j) take_any |= (G.a[j] >= 4 + P) & (U.code[j] != 0);
-    if (__builtin_amdgcn_ballot_w64(take_any) != 0) {
+    const bool take_ran = __builtin_amdgcn_ballot_w64(take_any) != 0;
+    if (take_ran) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int act = G.a[j];
@@ -66,6 +76,7 @@ __device__ __forceinline__ void step_group_state(const LdsWorld& w, const Key& q
             G.f[j] = (ok_take & !lt_tc) ? G.f[j] + (double)amount : G.f[j];
         }
     }
+    late(fb);
     uint32_t pos[4];
     int dst[4], cg[4];
     bool do_move[4], moved[4];
@@ -195,6 +206,7 @@ __device__ __forceinline__ void step_group_state(const LdsWorld& w, const Key& q
         U.dst[j] = dst[j];
         G.c[j] = cg[j];
     }
+    return take_ran;
 }
 
 // The stocks by cell code for the state-only steps' take checks: 256 (fuel, cargo) pairs,
@@ -208,6 +220,40 @@ __device__ __forceinline__ void stock_by_code(const LdsWorld& w, int2* take) {
     const int2 s = w.stock[min(k, P > 0 ? P - 1 : 0u)];  // P = 0: a word of the image, unused
     take[threadIdx.x] = k < P ? s : make_int2(0, 0);
 }
+
+// The wave's GATE pool (step_seq_kernel<kNt, kPool = true>). A GATE word is read only by
+// `fires = do_move & (cargo > 0) & (word <= thr)`, and in the flagship run about 7 of a wave's 64
+// lanes hold an env with cargo (profiles/seq_gatepool/carriers.json), so most lanes draw a block
+// nobody reads. The block depends on the quad's key and the counter alone, so any lane can draw
+// it ahead of time. When its pool is empty the wave votes: M = ballot(any of the lane's four
+// cargo > 0), m = popc(M).
+//   m == 0           no GATE draw, until a take ends the window;
+//   0 < m <= limit   a window of W steps, W the largest power of two <= 8 with m W <= 64: the
+//                    carriers write their GateSeed to the wave's seed row at their rank in M,
+//                    lane L draws carrier L >> log2 W's block at counter t + (L & (W - 1)) into
+//                    pool entry L, and for W steps every lane draws FUEL alone (draw_fuel) and
+//                    reads its GATE words from entry rank W + offset (one ds_read_b128);
+//   m > limit, or a wave with a lane past the last full group: kGateDirectRun steps of draw2,
+//                    then another vote.
+// A refill costs about two steps' GATE draws, so a wave whose takes keep ending its windows
+// (ships in port: right after a reset the take block runs on most wave-steps) must not refill
+// every step: after two refilled windows in a row that a take ended within kGateEarlyCut steps,
+// the wave draws directly for kGateDirectRun steps, and one more such window sends it there again.
+// cargo > 0 arises from cargo <= 0 only in a passed take of cargo, inside the take block
+// (arrival and loss only lower it), so a window ends early after a step whose take block ran
+// (step_group_state's result, a ballot: wave-uniform); the env that took did not move in that
+// step, so its gate could not fire in it. A lane that lost its cargo keeps a stale entry it no
+// longer tests. A window also ends with the run's inner steps (words drawn past them are never
+// read) and with the group. The rows are wave-private and one wave's LDS operations execute in
+// order, so there is no __syncthreads: wavefront-scope fences and wave barriers keep the
+// compiler's order. Per wave 64 pool entries and kGatePoolSeeds seed rows of 16 B.
+constexpr uint32_t kGatePoolLimit = 16;   // carrier lanes up to which a wave pools (W >= 4)
+constexpr uint32_t kGatePoolSeeds = 32;   // seed rows per wave: room for a limit of 32 (W = 2)
+constexpr uint32_t kGatePoolRow = 64 + kGatePoolSeeds;  // uint4 entries per wave
+constexpr uint32_t kGateDirectRun = 16;   // steps of the direct draw between two votes
+constexpr uint32_t kGateEarlyCut = 2;     // a refilled window that a take ends within this many steps was cut early
+constexpr size_t kGatePoolBytes = (kStepBlock / 64) * kGatePoolRow * sizeof(uint4);  // 6 KiB
+static_assert(kGatePoolLimit <= kGatePoolSeeds && kGatePoolLimit <= 32, "GATE pool: a window of at least 2 steps");
 
 // se_step_seq without auto-reset, fused: `steps` consecutive steps of the agent path in one
 // launch, on step_kernel's grid and ownership. Nothing outside the stream can observe the
@@ -224,7 +270,17 @@ __device__ __forceinline__ void stock_by_code(const LdsWorld& w, int2* take) {
 // and packed once after, and step steps - 1 alone runs the full one (step_group_agent<kKeep>).
 // Every launch of a split run therefore ends with a full step; steps == 1 is the full step by
 // itself.
-template <bool kNt>
+// The lane for a group's per-lane addresses. kOpaque (the pooled kernel): read through an empty
+// asm where it is used, so the byte offsets derived from it are computed there and not once
+// per launch, held across the step loops and spilled.
+template <bool kOpaque>
+__device__ __forceinline__ uint32_t seq_lane() {
+    uint32_t lane = threadIdx.x;
+    if constexpr (kOpaque) asm volatile("" : "+v"(lane));
+    return lane;
+}
+
+template <bool kNt, bool kPool>
 __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4))) void step_seq_kernel(
     StepArgs A, int32_t steps, int64_t ld) {
     extern __shared__ uint32_t lds[];
@@ -245,6 +301,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
     const LdsWorld w = stage_finish(A.world, A.dims, lds, st);
     // the state-only steps' take checks: the stocks by cell code, behind the staged image
     int2* const take = reinterpret_cast<int2*>(lds + A.dims.padded());
+    uint4* const gate_pool = reinterpret_cast<uint4*>(take + 256);  // kPool: behind the stock table
     if (steps > 1) {  // launch-uniform
         stock_by_code(w, take);
         __syncthreads();
@@ -262,7 +319,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
             asm volatile("" : "+v"(lane));
             G.template load<true>(A, At<true>{g0, 0, A.n}, lane);
         }
-        const At<true> at{g0, g * 4, A.n};
+        const At<true> at0{g0, g * 4, A.n};
         const uint32_t tl = A.t + (uint32_t)(steps - 1);  // the last step's counter
         if (steps > 1) {
             // steps 0 .. steps - 2, state only: x | y, origin and dest one register per env
@@ -281,15 +338,103 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
             PairInv inv = pair_invariants(qk);
             asm volatile("" : "+v"(inv.hi[0]), "+v"(inv.lo[0]), "+v"(inv.hi[1]), "+v"(inv.lo[1]));
             const int32_t* row = A.act;
-            for (uint32_t t = A.t; t != tl; ++t) {
-                // the next row's actions (there is one: the last step follows)
-                row += ld;
-                int32_t nxt[4];
-                ld4_full<kNt>(row, g0, nxt);
-                const U4x2 fg = draw2(qk, inv, t);
-                step_group_state(w, qk, t, fg.fuel, fg.gate, G, U);
+            if constexpr (!kPool) {
+                for (uint32_t t = A.t; t != tl; ++t) {
+                    // the next row's actions (there is one: the last step follows)
+                    row += ld;
+                    int32_t nxt[4];
+                    ld4_full<kNt>(row, g0, nxt);
+                    const U4x2 fg = draw2(qk, inv, t);
+                    step_group_state(w, qk, t, fg.fuel, fg.gate, G, U);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
+                    for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
+                }
+            } else {
+                // the wave's GATE pool (above): vote, then a window from the pool or a few
+                // steps of the direct draw, until the run's inner steps are done
+                const uint32_t lane = seq_lane<true>(), L = lane & 63u;
+                uint4* const pool = gate_pool + (lane >> 6) * kGatePoolRow;
+                uint4* const seeds = pool + 64;
+                // a wave with a lane past the last full group (the `break` above) has lanes
+                // missing from a refill: it draws directly
+                const bool whole = __builtin_amdgcn_ballot_w64(true) == ~0ull;
+                uint32_t cuts = 0;  // refilled windows in a row that a take cut early
+                for (uint32_t t = A.t; t != tl;) {
+                    // The pooled steps, window after window in one loop: the vote and the refill
+                    // are a block inside it, so the state stays in its registers from window to
+                    // window, and only a wave that leaves for the direct draw moves it.
+                    uint32_t win = 0, s = 0, wmask = 0;  // steps left in the window, its offset, W - 1
+                    const uint4* mine = pool;
+                    bool pooled = true, drew = false;
+                    do {
+                        if (win == 0) {
+                            const bool carry = (G.c[0] > 0) | (G.c[1] > 0) | (G.c[2] > 0) | (G.c[3] > 0);
+                            const uint64_t M = __builtin_amdgcn_ballot_w64(carry);
+                            const uint32_t m = (uint32_t)__popcll(M);
+                            if (!whole || m > kGatePoolLimit || (cuts >= 2 && m != 0)) {
+                                pooled = false;
+                                break;
+                            }
+                            drew = m != 0;
+                            // the window: the largest power of two W <= 8 with m W <= 64
+                            const uint32_t logw = m <= 8 ? 3u : m <= 16 ? 2u : 1u;
+                            const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
+                            wmask = (1u << logw) - 1u;
+                            if (m != 0) {
+                                if (carry) seeds[slot] = make_uint4(inv.c3, inv.hi[1], inv.lo[1], qk.e1);
+                                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                                __builtin_amdgcn_wave_barrier();
+                                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                                // lane L draws carrier L >> logw's block at window offset L & (W - 1);
+                                // past the last carrier: the last one's again, which nobody's gate reads
+                                const uint4 sd = seeds[min(L >> logw, m - 1u)];
+                                const U4 gw = draw_gate_pooled(qk.k0, qk.k1, GateSeed{sd.x, sd.y, sd.z, sd.w}, t + (L & wmask));
+                                pool[L] = make_uint4(gw.v[0], gw.v[1], gw.v[2], gw.v[3]);
+                                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                                __builtin_amdgcn_wave_barrier();
+                                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                            }
+                            // a carrier's words for offset s are entry slot W + s < 64. Another lane's
+                            // slot is at most m: it reads some entry below 64 + W (the seeds follow
+                            // the pool), whose words its gate never tests. m == 0: no entry holds
+                            // anything, no gate tests a word, and the window lasts until a take ends it.
+                            mine = pool + ((slot << logw) & 63u);
+                            win = m != 0 ? min(tl - t, wmask + 1u) : tl - t;  // t may wrap 2^32 inside the run
+                            s = 0;
+                        }
+                        row += ld;
+                        int32_t nxt[4];
+                        ld4_full<kNt>(row, g0, nxt, lane);
+                        const uint4 g4 = mine[s & wmask];
+                        // FUEL alone, drawn after the take block (step_group_state's `late`)
+                        const auto fuel = [&](U4& fb) {
+                            fb = draw_fuel(qk, inv, t);
+                            asm volatile("" : "+v"(fb.v[0]), "+v"(fb.v[1]), "+v"(fb.v[2]), "+v"(fb.v[3]));
+                        };
+                        const bool took = step_group_state(w, qk, t, U4{}, U4{{g4.x, g4.y, g4.z, g4.w}}, G, U, fuel);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
+                        ++s;
+                        ++t;
+                        if (took) {  // a take may have made a carrier: vote again (wave-uniform)
+                            cuts = drew && s <= kGateEarlyCut ? cuts + 1u : 0u;
+                            win = 0;
+                        } else if (--win == 0) {
+                            cuts = 0;
+                        }
+                    } while (t != tl);
+                    if (pooled) break;
+                    cuts = min(cuts, 1u);
+                    for (uint32_t n = min(tl - t, kGateDirectRun); n != 0; --n, ++t) {
+                        row += ld;
+                        int32_t nxt[4];
+                        ld4_full<kNt>(row, g0, nxt, lane);
+                        const U4x2 fg = draw2(qk, inv, t);
+                        step_group_state(w, qk, t, fg.fuel, fg.gate, G, U);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
+                    }
+                }
             }
             // back into the Group's packed bytes
             pack_pos(U.pos, G.x, G.y);
@@ -302,19 +447,21 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
         }
         // the last step in full: its reward, done and err are the run's
         StepOut O;
-        step_group_agent<false, true, kNt, false, false, true>(A, w, G, at, bs, F, early_draws<false>(A, g * 4, tl), tl, &O);
+        const uint32_t ln = seq_lane<kPool>();
+        const At<true> at = kPool ? At<true>{g0, (g0 + ln) * 4, A.n} : at0;
+        step_group_agent<false, true, kNt, false, false, true>(A, w, G, at, bs, F, early_draws<false>(A, kPool ? at.base : g * 4, tl), tl, &O);
         const se_state& S = late_args().st;
         __builtin_amdgcn_sched_barrier(0);  // the fuel halves back to back (store_moved)
-        st4u8_full(S.x, g0, G.x);
-        st4u8_full(S.y, g0, G.y);
-        st4_full(S.fuel, g0, G.f);
-        st4u8_full(S.done, g0, O.dn);
-        st4u8_full(reinterpret_cast<uint8_t*>(S.err), g0, O.ee);
+        st4u8_full(S.x, g0, G.x, ln);
+        st4u8_full(S.y, g0, G.y, ln);
+        st4_full(S.fuel, g0, G.f, ln);
+        st4u8_full(S.done, g0, O.dn, ln);
+        st4u8_full(reinterpret_cast<uint8_t*>(S.err), g0, O.ee, ln);
         __builtin_amdgcn_sched_barrier(0);
-        st4u8_full(S.origin, g0, G.org);
-        st4u8_full(S.dest, g0, G.dst);
-        st4_full(S.cargo, g0, G.c);
-        st4_full(S.reward, g0, O.rw);
+        st4u8_full(S.origin, g0, G.org, ln);
+        st4u8_full(S.dest, g0, G.dst, ln);
+        st4_full(S.cargo, g0, G.c, ln);
+        st4_full(S.reward, g0, O.rw, ln);
     }
 }
 
