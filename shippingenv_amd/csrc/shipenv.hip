@@ -34,6 +34,7 @@
 
 #include "../../include/shipenv.h"
 #include "philox.h"
+#include "step_lean.h"
 
 #ifndef SHIPENV_TRACE
 #define SHIPENV_TRACE 0  // 1 = diagnostic build: per-wave phase timestamps (tools/archive/wave_trace.py)

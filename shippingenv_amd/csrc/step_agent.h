@@ -45,17 +45,6 @@ __device__ __forceinline__ uint32_t cell_of(uint32_t p, uint32_t wh) {
     return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, p), __builtin_bit_cast(u16x2, wh), 0u, false);
 }
 
-// A lane predicate with its complement, for the state-only step: the compare is made once and
-// the complement is an s_not of its lane mask (written `!c`, the compiler folds the negation
-// into a second, inverted v_cmp). Inactive lanes read either way; both bits are per-lane values.
-struct Pred2 {
-    bool t, f;
-};
-__device__ __forceinline__ Pred2 with_complement(bool c) {
-    uint64_t m = __builtin_amdgcn_ballot_w64(c);
-    asm("" : "+s"(m));
-    return Pred2{__builtin_amdgcn_inverse_ballot_w64(m), __builtin_amdgcn_inverse_ballot_w64(~m)};
-}
 // The byte at index x * W + y of an LDS table, the table's LDS address riding in the dot
 // product's accumulator (cell_of, then the pointer add, is one more v_add_u32 of a base that is
 // zero). cell0: lds_address(table).

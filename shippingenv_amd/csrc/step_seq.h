@@ -13,14 +13,15 @@
 // The state-only step: a step of a fused sequence before its last, for a full group, Philox
 // draws, no auto-reset. Nothing can read an inner step's reward, done or err, and the next state
 // needs neither the out-of-fuel flag (a dead ship keeps moving) nor which error was raised, only
-// whether one was. So there is no reward, no out-of-fuel compare, and the action's checks are one
-// bit. The state arithmetic, its order and every Philox counter are step_group_agent's.
+// whether one was. So there is no reward, no out-of-fuel compare, and the action's checks are two
+// bits. The state arithmetic, its order and every Philox counter are step_group_agent's.
 // Position, origin and dest live in Carried from step to step, one register per env, so
 // consecutive steps neither unpack nor pack bytes; fuel, cargo and the action are G's (of G the
 // step touches f, c and a only). The cell code under the ship is carried too (after a move
 // it is the byte the ground test read at the cell moved to), so a step makes one cell lookup per
-// env, with the table's LDS address riding in the dot product (lds_cell). The complements of the
-// action-range compares are s_not of their lane masks (with_complement). The caller draws FUEL
+// env, with the table's LDS address riding in the dot product (lds_cell). The action is decoded
+// by two unsigned range compares and the fuel update is one FMA (step_lean.h); each env's gate
+// threshold is carried and looked up again only where its cargo changes. The caller draws FUEL
 // and GATE together (fb, gb: philox.h, draw2), or takes gb from its wave's GATE pool and lets
 // `late` draw FUEL (below). The ranked LOSS draw is step_group_agent's, line
 // for line: as a shared helper it compiled to another instruction order in both steps.
@@ -32,8 +33,16 @@ struct Carried {
     uint32_t pos[4];  // x | y << 16
     int org[4], dst[4];
     uint32_t code[4];   // the cell code under the ship, w.cell[cell_of(pos)]
+    uint32_t thr[4];    // the gate threshold of the env's cargo, gate_thr_of(w, cargo)
     const int2* take;   // the block's stocks by cell code (stock_by_code), the same for every env
 };
+// Carried::thr. Cargo changes in three places only, all rare and each behind a branch (a passed
+// take, a loss, an arrival), so the threshold is looked up there and where Carried is filled, and
+// the gate test of every step reads a register. Entry 0 is 0, which a word can equal: the test
+// keeps its cargo > 0.
+__device__ __forceinline__ uint32_t gate_thr_of(const LdsWorld& w, int cargo) {
+    return w.gate_thr[min(max(cargo, 0), 50)];
+}
 // `late` runs after the take block and may set fb: the pooled kernel draws FUEL there and pins
 // the words, which keeps the draw out of the step's last block and, as it happens, cargo and fuel
 // in their registers across the take block (drawn before the call the loop had 10 VALU more, 7
@@ -74,6 +83,7 @@ __device__ __forceinline__ bool step_group_state(const LdsWorld& w, const Key& q
             const bool ok_take = (act >= 4 + P) & (amount > 0) & (amount <= stock);
             G.c[j] = (ok_take & lt_tc) ? G.c[j] + amount : G.c[j];
             G.f[j] = (ok_take & !lt_tc) ? G.f[j] + (double)amount : G.f[j];
+            U.thr[j] = gate_thr_of(w, G.c[j]);
         }
     }
     late(fb);
@@ -84,9 +94,7 @@ __device__ __forceinline__ bool step_group_state(const LdsWorld& w, const Key& q
     for (int j = 0; j < 4; ++j) {
         // [0,4) moves (-4..-1 wrap), [4, 4+P) SELECT; the takes are done
         const int act = G.a[j];
-        const bool bad = act < -4;
-        const Pred2 mv = with_complement(act < 4), sel = with_complement(act < 4 + P);
-        const int val = act - 4;  // only a select reads it
+        const int val = (int)((uint32_t)act - 4u);  // only a select reads it
         const uint32_t dxy = w.moves[act & 3];
         const uint32_t p = U.pos[j];
         dst[j] = U.dst[j];
@@ -100,17 +108,14 @@ __device__ __forceinline__ bool step_group_state(const LdsWorld& w, const Key& q
         // carried as a full register (as a byte it is masked again before every select)
         asm("" : "+v"(code_cp));
         const bool ground = code_cp == kCellGround;  // :293
-        // step_group_agent's error cascade as its one bit: no check of the action's own type
-        // failed (mask arithmetic, no ?: : a branch here would take the LDS lookups with it).
-        // A take is not among them: the take guard has applied it, and nothing below reads
-        // whether a take passed.
+        // step_group_agent's error cascade as the two bits the next state needs (step_lean.h):
+        // a move that passed its checks, a SELECT that passed its own (mask arithmetic, no
+        // ?: : a branch here would take the LDS lookups with it). A take is not among them: the
+        // take guard has applied it, and nothing below reads whether a take passed.
         const bool same = U.org[j] == val;
-        const bool ok_mv = mv.t & !nodest & inb;
-        const bool ok_sel = mv.f & sel.t & !same;
-        const bool ok = !bad & (P != 0) & (ok_mv | ok_sel);
-        do_move[j] = ok & mv.t;
+        do_move[j] = lean_do_move(act, P, nodest, inb);
         moved[j] = do_move[j] & !ground;
-        const bool sel_ok = ok & mv.f & sel.t;
+        const bool sel_ok = lean_sel_ok(act, P, same);
         pos[j] = moved[j] ? cp : p;
         U.code[j] = moved[j] ? code_cp : U.code[j];  // the ground test's read
         dst[j] = sel_ok ? val : dst[j];
@@ -135,10 +140,9 @@ __device__ __forceinline__ bool step_group_state(const LdsWorld& w, const Key& q
     for (int j = 0; j < 4; ++j) {
         // fuel cost (:103-104); a ship that does not move adds -0.0, which leaves every value as it is
         const double scale = 1.0 + (-0.1 + (double)fb.v[j] * kFifthPerWord);
-        f[j] = G.f[j] + (moved[j] ? -scale : -0.0);
-        // the gate (:318-323), as step_group_agent tests it
-        const uint32_t thr = w.gate_thr[min(max(cg[j], 0), 50)];
-        const bool fires = do_move[j] & (cg[j] > 0) & (gb.v[j] <= thr);
+        f[j] = lean_fuel(G.f[j], scale, moved[j]);
+        // the gate (:318-323), as step_group_agent tests it, against the carried threshold
+        const bool fires = do_move[j] & (cg[j] > 0) & (gb.v[j] <= U.thr[j]);
         fire |= (uint32_t)fires << j;
     }
     // the flags travel as opaque VGPR bit masks (no lane masks live in SGPR pairs
@@ -187,6 +191,7 @@ __device__ __forceinline__ bool step_group_state(const LdsWorld& w, const Key& q
             const int loss = lt[j] < kTypeLo ? 0 : some;
             const bool fj = (fire >> j) & 1u;
             cg[j] = fj ? cg[j] - loss : cg[j];
+            U.thr[j] = gate_thr_of(w, cg[j]);
         }
     }
     if (arrive) {
@@ -196,6 +201,7 @@ __device__ __forceinline__ bool step_group_state(const LdsWorld& w, const Key& q
             const bool aj = (arrive >> j) & 1u;
             const int nd = pick_other(ab.v[j], P, dst[j]);
             cg[j] = aj ? 0 : cg[j];
+            U.thr[j] = gate_thr_of(w, cg[j]);
             org[j] = aj ? dst[j] : org[j];
             dst[j] = aj ? nd : dst[j];
         }
@@ -330,6 +336,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                 U.org[j] = byte_of(G.org, j);
                 U.dst[j] = byte_of(G.dst, j);
                 U.code[j] = w.cell[cell_of(U.pos[j], (uint32_t)w.W | (1u << 16))];
+                U.thr[j] = gate_thr_of(w, G.c[j]);
             }
             U.take = take;
             // the step-invariant parts of the quad's FUEL and GATE blocks (philox.h, draw2),
