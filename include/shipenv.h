@@ -319,6 +319,46 @@ int se_sample_actions(se_env* env, int32_t* type, int32_t* a, int32_t* b, uint32
 int se_rollout(se_env* env, const int32_t* src, int64_t m, int32_t max_steps, int32_t max_attempts,
                int64_t rollout_base, double* ret, int32_t* steps, int32_t* status, void* stream);
 
+/* Scripted rollouts: what happens to env src[r] if it plays this action sequence, without
+ * playing it. Rollout r starts from a copy of env src[r]'s state (the env's state and counters
+ * are not modified) and plays its plan, position k = 0 .. len - 1 in turn:
+ *   - a step that raises (err != SE_ERR_OK) leaves the copy untouched, adds no reward, is not
+ *     counted and adds 1 to raised (se_rollout's `except Exception: continue`); the plan goes on;
+ *   - any other step adds its f64 reward to ret[r] in order and 1 to counted[r]; if it reports
+ *     done the rollout ends there with SE_PLAN_DONE and the rest of the plan is not played.
+ * Plans are step-major: the action of position k of rollout r is element k * ld + r, ld >= m,
+ * rows 16-byte aligned (the arrays, and ld a multiple of 4 when steps > 1). Two encodings:
+ *   typed        type, a, b as se_step_typed takes them; a type outside 1..4 raises
+ *                SE_ERR_BAD_CATEGORY as there, so type 0 pads a plan;
+ *   agent index  a == b == NULL and type holds agent indices as se_step takes them; an index
+ *                below -4 raises SE_ERR_BAD_INDEX as there.
+ * len (NULL: steps for every rollout) gives each rollout's plan length, clamped to [0, steps].
+ * Outputs (device, m entries): ret, counted, status = SE_PLAN_*, and what `out` asks for.
+ * Draws: Philox(seed, id) with id = ids ? ids[r] : rollout_base + r (equal ids give common
+ * random numbers). Position k reads (k, slot 12) words 1-3: u_fuel, u_gate, u_type; and, for a
+ * partial loss or an arrival, (k, slot 13): three beta uniforms, the new destination. Word 0 of
+ * slot 12, se_rollout's sample word, is not read. The counter is the plan position, raising
+ * steps included, so these are the draws of attempt k of se_rollout's rollout with the same id:
+ * a scripted rollout whose plan is that rollout's attempt list equals it in ret (bits), steps,
+ * done-ness and the final ship.
+ * Misuse (a null required buffer with m > 0, ld < m, a negative m, steps or rollout_base, one
+ * of a / b NULL, misaligned rows) is SE_EINVAL before any launch; m = 0 is a no-op; steps = 0
+ * writes ret 0, counted 0 and SE_PLAN_END. The call allocates nothing and does not synchronise:
+ * it may be captured into a graph. */
+#define SE_PLAN_DONE 0     /* a counted step reported done; later actions not played */
+#define SE_PLAN_END 1      /* the plan ran out */
+#define SE_PLAN_BAD_SRC 4  /* src[r] outside [0, n): ret 0, steps 0, nothing else written but zeros/-1 */
+typedef struct se_plan_out {   /* every pointer may be NULL: not wanted; m entries each */
+    int32_t *raised, *first_err, *first_err_at;   /* count; SE_ERR_* of the first raising step (0) and its position (-1) */
+    int32_t *x, *y; double *fuel; int32_t *cargo, *origin, *dest;  /* the ship when the rollout ended, -1 = None;
+                                                                      a bad source: fuel 0, the others -1 */
+} se_plan_out;
+int se_rollout_plan(se_env* env, const int32_t* src, int64_t m,
+                    const int32_t* type, const int32_t* a, const int32_t* b,  /* a == b == NULL: type holds agent indices */
+                    int64_t ld, int32_t steps, const int32_t* len /* NULL: steps; else clamped to [0, steps] */,
+                    const int64_t* ids /* NULL: rollout_base + r */, int64_t rollout_base,
+                    double* ret, int32_t* counted, int32_t* status, const se_plan_out* out, void* stream);
+
 /* One MCTS decision per env (agents/mcts.py:240-292, MCTSAgent.choose_action): `simulations`
  * sequential simulations (UCB1 selection with c_param, one expansion, a random rollout of at
  * most max_rollout_steps counted steps, backpropagation) on a private copy of the env, whose

@@ -29,6 +29,8 @@ USED_FUEL_GATE, USED_LOSS_TYPE, USED_BETA, USED_ARRIVE, USED_MOVED = 1, 2, 4, 8,
 # se_sample_actions special types, se_rollout statuses
 SAMPLE_RAISES, SAMPLE_NO_OTHER_PORT = -1, -2
 ROLL_DONE, ROLL_MAX_STEPS, ROLL_RAISED, ROLL_ATTEMPTS, ROLL_BAD_SRC = 0, 1, 2, 3, 4
+# se_rollout_plan statuses
+PLAN_DONE, PLAN_END, PLAN_BAD_SRC = 0, 1, 4
 # se_mcts_choose statuses
 MCTS_OK, MCTS_CUT, MCTS_RAISED, MCTS_NEVER_RETURNS = 0, 1, 2, 3
 MCTS_MAX_SIMULATIONS = 256
@@ -43,7 +45,7 @@ SERVER_STEP, SERVER_RESET_TO = 1, 2
 EXPORTS = (
     "se_create", "se_set_ports", "se_bind", "se_reset", "se_reset_to", "se_step", "se_step_seq", "se_step_seq_mark",
     "se_step_typed", "se_step_replay", "se_step_agent_replay", "se_observe", "se_valid_mask", "se_gen_actions",
-    "se_sample_actions", "se_rollout", "se_mcts_create", "se_mcts_choose", "se_mcts_destroy",
+    "se_sample_actions", "se_rollout", "se_rollout_plan", "se_mcts_create", "se_mcts_choose", "se_mcts_destroy",
     "se_sarsa_create", "se_sarsa_layout", "se_sarsa_bind", "se_sarsa_step", "se_sarsa_choose", "se_sarsa_destroy",
     "se_qnet_create", "se_qnet_set_weights", "se_policy", "se_policy_f32",
     "se_qnet_repack", "se_policy_record", "se_policy_record_f32",
@@ -79,6 +81,12 @@ class SeSarsaState(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("type", "a", "b", "fresh", "ep_len", "ep_return")]
 
 
+class SePlanOut(C.Structure):
+    """se_plan_out: what se_rollout_plan writes beside ret, counted and status (NULL: not wanted)."""
+    _fields_ = [(name, C.c_void_p) for name in (
+        "raised", "first_err", "first_err_at", "x", "y", "fuel", "cargo", "origin", "dest")]
+
+
 class SeDoneRec(C.Structure):
     _fields_ = [("env", C.c_int32), ("ep_return", C.c_float), ("ep_len", C.c_int32),
                 ("step", C.c_int32)]
@@ -106,6 +114,7 @@ def _declare(lib):
         "se_gen_actions": [P, P, u32, P],
         "se_sample_actions": [P, P, P, P, u32, P],
         "se_rollout": [P, P, i64, i32, i32, i64, P, P, P, P],
+        "se_rollout_plan": [P, P, i64, P, P, P, i64, i32, P, P, i64, P, P, P, C.POINTER(SePlanOut), P],
         "se_mcts_create": [C.POINTER(P), P, i32],
         "se_mcts_choose": [P, i32, C.c_double, i32, i32, i64, P, P, P, P, P, P, P],
         "se_mcts_destroy": [P],

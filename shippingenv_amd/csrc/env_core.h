@@ -81,7 +81,9 @@ struct Pending {
 constexpr double kFifthPerWord = 0x1.999999999999ap-35;  // fl(0.2) * 2^-32
 static_assert(kFifthPerWord * 4294967296.0 == 0.2, "0.2 * 2^-32 must be exact");
 
-template <bool kUnitMoves, bool kReplay>
+// kUnitCost: the caller knows the move, if the action is one, is a unit move (distance 1: no
+// square root); it follows kUnitMoves unless a caller has checked its arbitrary moves itself.
+template <bool kUnitMoves, bool kReplay, bool kUnitCost = kUnitMoves>
 __host__ __device__ __forceinline__ Pending env_begin(const LdsWorld& w, Ship& s, int e_in, int type, int a,
                                              int b, double u_fuel, double u_gate, uint32_t gw) {
     // --- MOVE (_move_ship :273-339)
@@ -94,7 +96,7 @@ __host__ __device__ __forceinline__ Pending env_begin(const LdsWorld& w, Ship& s
     // fuel cost (:103-104): dist * (1 + uniform(-0.1, 0.1)), uniform = -0.1 + 0.2*u, unfused
     const double fifth_u = kReplay ? 0.2 * u_fuel : u_fuel * kFifthPerWord;
     const double scale = 1.0 + (-0.1 + fifth_u);
-    const double cost = kUnitMoves ? scale : int_sqrt_rn(big ? 1 : a * a + b * b) * scale;
+    const double cost = kUnitCost ? scale : int_sqrt_rn(big ? 1 : a * a + b * b) * scale;
     const bool out_of_fuel = s.fuel < cost;  // :288-290
     const bool ground = w.is_ground(cx, cy);  // :293: blocked (-5) or moved (-0.0001 then -1)
     const int mx = ground ? s.x : cx, my = ground ? s.y : cy;

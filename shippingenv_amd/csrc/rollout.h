@@ -85,10 +85,14 @@ struct RolloutArgs {
 // One step of a private env copy from its drawn block d (words 1-3: u_fuel, u_gate, u_type)
 // and, for a partial loss or an arrival, the block at (t, slot_b): three beta uniforms, the
 // new destination. The step of a rollout attempt and of an MCTS tree step (mcts.h). A
-// raising step (p.e != SE_ERR_OK) leaves s untouched.
+// raising step (p.e != SE_ERR_OK) leaves s untouched. kUnitMoves: the action is one the random
+// policy or a decoded agent index can name (a unit move, a port in range, a type in 1..4);
+// plan.h's typed plans are not, and its agent plans hand their decode error in as e_in.
+template <bool kUnitMoves = true, bool kUnitCost = kUnitMoves>
 __device__ __forceinline__ Pending drawn_step(const LdsWorld& w, Ship& s, const Key& key, uint32_t t,
-                                              uint32_t slot_b, const U4& d, int ty, int va, int vb) {
-    Pending p = env_begin<true, false>(w, s, SE_ERR_OK, ty, va, vb, (double)d.v[1], 0.0, d.v[2]);
+                                              uint32_t slot_b, const U4& d, int ty, int va, int vb,
+                                              int e_in = SE_ERR_OK) {
+    Pending p = env_begin<kUnitMoves, false, kUnitCost>(w, s, e_in, ty, va, vb, (double)d.v[1], 0.0, d.v[2]);
     if (p.e != SE_ERR_OK) return p;
     const int total_kind = d.v[3] > kTypeHi ? kLossTotal : kLossPartial;
     const int kind = d.v[3] < kTypeLo ? kLossNone : total_kind;

@@ -74,6 +74,7 @@ constexpr double kMaxCargo = 50.0;
 #include "step_seq.h"     // step_group_state, step_seq_kernel, step_tail_seq_kernel
 #include "views.h"        // done-list copy, reset, observe, valid masks, gen_actions
 #include "rollout.h"      // random policy, rollouts, episode statistics
+#include "plan.h"         // scripted rollouts: the rollout loop with its actions read from memory
 }  // namespace
 
 // ====================================================================== host side
@@ -766,6 +767,59 @@ int se_rollout(se_env* env, const int32_t* src, int64_t m, int32_t max_steps, in
     A.steps = steps;
     A.status = status;
     rollout_kernel<<<grid_for(m), kBlock, lds_bytes(env), (hipStream_t)stream>>>(A);
+    HIP_TRY(hipGetLastError());
+    return SE_OK;
+}
+
+int se_rollout_plan(se_env* env, const int32_t* src, int64_t m, const int32_t* type, const int32_t* a,
+                    const int32_t* b, int64_t ld, int32_t steps, const int32_t* len, const int64_t* ids,
+                    int64_t rollout_base, double* ret, int32_t* counted, int32_t* status,
+                    const se_plan_out* out, void* stream) {
+    // the arguments first: misuse is reported whatever the env's state
+    if (m < 0 || steps < 0 || rollout_base < 0)
+        return fail(SE_EINVAL, "m, steps and rollout_base must be >= 0");
+    if ((a == nullptr) != (b == nullptr))
+        return fail(SE_EINVAL, "a and b go together: both for typed actions, neither for agent indices");
+    if (ld < m) return fail(SE_EINVAL, "row stride must be >= m");
+    if (m > 0 && (!src || !ret || !counted || !status || (steps > 0 && !type)))
+        return fail(SE_EINVAL, "null plan buffer");
+    if (!aligned16(type) || !aligned16(a) || !aligned16(b) || (steps > 1 && (ld & 3)))
+        return fail(SE_EINVAL, "plan rows must be 16-byte aligned (row stride a multiple of 4)");
+    int rc = check_ready(env);
+    if (rc) return rc;
+    if (m == 0) return SE_OK;
+    DeviceGuard g(env->device);
+    const bool agent = a == nullptr;
+    const size_t lds = lds_bytes(env);
+    if (lds > 160 * 1024) return fail(SE_EINVAL, "the world image exceeds the LDS");
+    if (lds > 64 * 1024) {  // once per kernel and device: no call on the launch path after the first
+        static std::atomic<uint64_t> lds_typed{0}, lds_agent{0};
+        rc = agent ? allow_dynamic_lds(lds_agent, reinterpret_cast<const void*>(plan_kernel<true>), 160 * 1024, env->device)
+                   : allow_dynamic_lds(lds_typed, reinterpret_cast<const void*>(plan_kernel<false>), 160 * 1024, env->device);
+        if (rc) return rc;
+    }
+    PlanArgs A{};
+    A.world = env->d_world;
+    A.dims = env->dims;
+    A.n = env->n;
+    A.m = m;
+    A.ld = ld;
+    A.rollout_base = rollout_base;
+    A.seed = env->seed;
+    A.steps = steps;
+    A.st = env->st;
+    A.src = src;
+    A.type = type;
+    A.a = a;
+    A.b = b;
+    A.len = len;
+    A.ids = ids;
+    A.ret = ret;
+    A.counted = counted;
+    A.status = status;
+    if (out) A.out = *out;
+    const auto kernel = agent ? plan_kernel<true> : plan_kernel<false>;
+    kernel<<<grid_for(m), kBlock, lds, (hipStream_t)stream>>>(A);
     HIP_TRY(hipGetLastError());
     return SE_OK;
 }

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import random as _random
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -25,6 +26,23 @@ TAPE_DTYPE = np.dtype(
     [("u_fuel", "<f8"), ("u_gate", "<f8"), ("u_type", "<f8"), ("beta", "<f8"),
      ("arrive_dest", "<i4"), ("used", "<i4")]
 )  # se_tape
+
+
+class PlanResult(NamedTuple):
+    """What VecEnv.rollout_plan returns: device tensors of m entries (the ship's six are None
+    without return_end)."""
+    ret: torch.Tensor           # f64: the counted steps' rewards summed in order
+    steps: torch.Tensor         # counted steps
+    status: torch.Tensor        # PLAN_DONE / PLAN_END / PLAN_BAD_SRC
+    raised: torch.Tensor        # raising steps (skipped)
+    first_err: torch.Tensor     # ERR_* of the first raising step, 0 if none
+    first_err_at: torch.Tensor  # its plan position, -1 if none
+    x: Optional[torch.Tensor] = None
+    y: Optional[torch.Tensor] = None
+    fuel: Optional[torch.Tensor] = None
+    cargo: Optional[torch.Tensor] = None
+    origin: Optional[torch.Tensor] = None
+    dest: Optional[torch.Tensor] = None
 
 
 def draw_port_stocks(n_ports, seed):
@@ -334,6 +352,63 @@ class VecEnv:
                                    self._stream()))
         self._keep = s
         return ret, steps, status
+
+    def _plan_rows(self, t, m, what):
+        """An int32 [K, m] device tensor with 16-byte aligned rows, as step_seq takes its rows."""
+        if not (type(t) is torch.Tensor and t.dtype is torch.int32 and t.is_cuda and t.dim() == 2
+                and t.get_device() == self._dev_index and t.shape[1] == m
+                and (t.numel() == 0 or (t.stride(1) == 1 and t.data_ptr() % 16 == 0
+                                        and (t.shape[0] < 2 or t.stride(0) % 4 == 0)))):
+            raise ValueError(f"rollout_plan needs {what} as an int32 [K, {m}] device tensor with 16-byte aligned rows")
+        return t
+
+    def rollout_plan(self, src, type=None, a=None, b=None, *, actions=None, lengths=None, ids=None,
+                     rollout_base=0, return_end=False):
+        """Scripted rollouts (se_rollout_plan): rollout r plays column r of a plan on a private
+        copy of env src[r] (int32 [m]); env state and counters are untouched. The plan is int32
+        device tensors [K, m] with 16-byte aligned rows, either typed (type, a, b: step_typed's
+        encoding; type 0 is a pad that raises) or actions= (agent indices: step's encoding).
+        lengths (int32 [m]) cuts each plan short (clamped to [0, K]); ids (int64 [m]) names each
+        rollout's Philox stream instead of rollout_base + r: rollouts with equal ids share their
+        random numbers. A raising step is skipped (counted in `raised`), a step that reports
+        done ends the rollout (status PLAN_DONE, else PLAN_END; PLAN_BAD_SRC for a bad source).
+        Position k draws what attempt k of rollout()'s rollout with the same id draws, so that
+        rollout's attempt list as a plan reproduces it bit for bit. Returns a PlanResult of
+        fresh device tensors: ret f64, steps, status, raised, first_err, first_err_at and, with
+        return_end, the ship each rollout ended with (x, y, fuel, cargo, origin, dest; -1 = None),
+        otherwise None in those fields."""
+        if not isinstance(src, torch.Tensor):
+            src = torch.as_tensor(np.asarray(src))
+        m = src.numel()
+        s = self._dev(src, torch.int32, count=m)
+        typed = (type, a, b)
+        if actions is not None:
+            if any(v is not None for v in typed):
+                raise ValueError("rollout_plan takes either (type, a, b) or actions=, not both")
+            rows = (self._plan_rows(actions, m, "actions"), None, None)
+        else:
+            if any(v is None for v in typed):
+                raise ValueError("rollout_plan needs the typed plan (type, a, b) or actions=")
+            rows = tuple(self._plan_rows(v, m, f) for v, f in zip(typed, ("type", "a", "b")))
+            if len({(v.shape[0], v.stride(0)) for v in rows}) != 1:
+                raise ValueError("type, a and b must have one shape and one row stride")
+        K = rows[0].shape[0]
+        ld = rows[0].stride(0) if K > 1 and m > 0 else (m + 3) // 4 * 4
+        ln = None if lengths is None else self._dev(lengths, torch.int32, count=m)
+        idt = None if ids is None else self._dev(ids, torch.int64, count=m)
+        kw = dict(dtype=torch.int32, device=self.device)
+        ret = torch.empty(m, dtype=torch.float64, device=self.device)
+        steps, status, raised, first_err, first_at = (torch.empty(m, **kw) for _ in range(5))
+        end = (None,) * 6
+        if return_end:
+            end = tuple(torch.empty(m, dtype=torch.float64 if f == "fuel" else torch.int32, device=self.device)
+                        for f in ("x", "y", "fuel", "cargo", "origin", "dest"))
+        out = N.SePlanOut(*[None if t is None else t.data_ptr() for t in (raised, first_err, first_at) + end])
+        N.check(N.lib().se_rollout_plan(self._h, _ptr(s), m, _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]), ld, K,
+                                        _ptr(ln), _ptr(idt), int(rollout_base), _ptr(ret), _ptr(steps),
+                                        _ptr(status), C.byref(out), self._stream()))
+        self._keep = (s, rows, ln, idt)
+        return PlanResult(ret, steps, status, raised, first_err, first_at, *end)
 
     def episode_stats(self):
         """Device f64[3] {sum of returns, episodes, sum of lengths} since the last clear."""
