@@ -41,27 +41,6 @@ SARSA_MAX_ATTEMPTS = 64
 # se_server_call ops
 SERVER_STEP, SERVER_RESET_TO = 1, 2
 
-# every symbol include/shipenv.h declares
-EXPORTS = (
-    "se_create", "se_set_ports", "se_bind", "se_reset", "se_reset_to", "se_step", "se_step_seq", "se_step_seq_mark",
-    "se_step_typed", "se_step_replay", "se_step_agent_replay", "se_observe", "se_valid_mask", "se_gen_actions",
-    "se_sample_actions", "se_rollout", "se_rollout_plan", "se_mcts_create", "se_mcts_choose", "se_mcts_destroy",
-    "se_sarsa_create", "se_sarsa_layout", "se_sarsa_bind", "se_sarsa_step", "se_sarsa_choose", "se_sarsa_destroy",
-    "se_qnet_create", "se_qnet_set_weights", "se_policy", "se_policy_f32",
-    "se_qnet_repack", "se_policy_record", "se_policy_record_f32",
-    "se_qnet_destroy", "se_replay_create", "se_replay_begin", "se_replay_end", "se_replay_end_reset", "se_step_record",
-    "se_replay_size",
-    "se_replay_sample", "se_replay_destroy", "se_qtrain_create", "se_qtrain_bind", "se_qtrain_pack",
-    "se_qtrain_step", "se_qtrain_step_policy", "se_qtrain_step_replay", "se_qtrain_grad_size", "se_qtrain_grad", "se_qtrain_apply",
-    "se_qtrain_destroy",
-    "se_episode_stats", "se_clear_stats", "se_done_layout", "se_done_list", "se_done_compact",
-    "se_get_counters", "se_set_counters",
-    "se_map_decode_luma", "se_map_area_threshold", "se_map_from_jpeg",
-    "se_host_create", "se_host_set_ports", "se_host_step_replay", "se_host_reset_to", "se_host_destroy",
-    "se_host_alloc", "se_host_free", "se_server_create", "se_server_call", "se_server_launches", "se_server_destroy",
-    "se_destroy", "se_last_error", "se_abi_version",
-)
-
 
 class NativeLibraryError(RuntimeError):
     pass
@@ -95,92 +74,101 @@ class SeDoneRec(C.Structure):
 _LIB = None
 
 
+# Every symbol include/shipenv.h declares, with its argument types. The result type is int (a
+# status) but for the two in _RESTYPES.
+_P, _i32, _i64, _u32, _u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
+SIGNATURES = {
+    "se_create": [C.POINTER(_P), C.c_int, _i64, _i64, _i32, _i32, _P, _i32, _P, _P, _P, _P, _u64, _u32],
+    "se_set_ports": [_P, _i32, _P, _P, _P, _P],
+    "se_bind": [_P, C.POINTER(SeState)],
+    "se_reset": [_P, _P, _P],
+    "se_reset_to": [_P, _P, _P, _P, _P],
+    "se_step": [_P, _P, _P],
+    "se_step_seq": [_P, _P, _i64, _i32, _P],
+    "se_step_seq_mark": [_P, _P, _i64, _i32, _P, _P, _i32],
+    "se_step_typed": [_P, _P, _P, _P, _P],
+    "se_step_replay": [_P, _P, _P, _P, _P, _P],
+    "se_step_agent_replay": [_P, _P, _P, _P],
+    "se_observe": [_P, _P, _i64, _P],
+    "se_valid_mask": [_P, _P, _P],
+    "se_gen_actions": [_P, _P, _u32, _P],
+    "se_sample_actions": [_P, _P, _P, _P, _u32, _P],
+    "se_rollout": [_P, _P, _i64, _i32, _i32, _i64, _P, _P, _P, _P],
+    "se_rollout_plan": [_P, _P, _i64, _P, _P, _P, _i64, _i32, _P, _P, _i64, _P, _P, _P, C.POINTER(SePlanOut), _P],
+    "se_mcts_create": [C.POINTER(_P), _P, _i32],
+    "se_mcts_choose": [_P, _i32, C.c_double, _i32, _i32, _i64, _P, _P, _P, _P, _P, _P, _P],
+    "se_mcts_destroy": [_P],
+    "se_sarsa_create": [C.POINTER(_P), _P, _i64],
+    "se_sarsa_layout": [_P, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)],
+    "se_sarsa_bind": [_P, _P, C.POINTER(SeSarsaState)],
+    "se_sarsa_step": [_P, C.c_double, C.c_double, C.c_double, _i32, _i32, _i32, _u32, _P, _P, _P, _P, _P, _P],
+    "se_sarsa_choose": [_P, C.c_double, _u32, _P, _P, _P, _P],
+    "se_sarsa_destroy": [_P],
+    "se_qnet_create": [C.POINTER(_P), _P],
+    "se_qnet_set_weights": [_P, _P, _P, _P, _P, _P, _P, _P],
+    "se_policy": [_P, _P, C.c_double, _u32, _P, _i64, _P],
+    "se_policy_f32": [_P, _P, C.c_double, _u32, _P, _i64, _P],
+    "se_qnet_repack": [_P, _P, _P],
+    "se_policy_record": [_P, _P, _P, C.c_double, _u32, _P],
+    "se_policy_record_f32": [_P, _P, _P, C.c_double, _u32, _P],
+    "se_qnet_destroy": [_P],
+    "se_replay_create": [_P, _P, _i64],
+    "se_replay_begin": [_P, _P, _P],
+    "se_replay_end": [_P, _P, C.c_int32, _P],
+    "se_replay_end_reset": [_P, _P, C.c_int32, _P],
+    "se_step_record": [_P, _P, _P, C.c_int32, _P],
+    "se_replay_size": [_P, _P, _P],
+    "se_replay_sample": [_P, _i64, _P, _u32, _P, _P, _P, _P, _P, _P, _P],
+    "se_replay_destroy": [_P],
+    "se_qtrain_create": [_P, _P, _i64],
+    "se_qtrain_bind": [_P, _P, _P, _P, _P, _P],
+    "se_qtrain_pack": [_P, C.c_int32, _P],
+    "se_qtrain_step": [_P, _i64, _P, _P, _P, _P, _P, _P] + [C.c_float] * 5 + [_P, _P, _P],
+    "se_qtrain_step_policy": [_P, _P, _i64, _P, _P, _P, _P, _P, _P] + [C.c_float] * 5 + [_P, _P, _P],
+    "se_qtrain_step_replay": [_P, _P, _P, _i64] + [C.c_float] * 5 + [_P, _i64, _P, _P],
+    "se_qtrain_grad_size": [_P],
+    "se_qtrain_grad": [_P, _i64, _P, _P, _P, _P, _P, _P, C.c_float, _P, _P],
+    "se_qtrain_apply": [_P, _P, _P] + [C.c_float] * 4 + [_P, _P, _P],
+    "se_qtrain_destroy": [_P],
+    "se_episode_stats": [_P, _P, _P],
+    "se_clear_stats": [_P, _P],
+    "se_done_layout": [_P, C.POINTER(_i64), C.POINTER(_i32)],
+    "se_done_list": [_P, C.POINTER(_i64), C.POINTER(_i64)],
+    "se_done_compact": [_P, _P, _P, _P],
+    "se_get_counters": [_P, C.POINTER(_u64), C.POINTER(_u64)],
+    "se_set_counters": [_P, _u64, _u64],
+    "se_map_decode_luma": [C.c_char_p, C.c_size_t, _P, C.c_size_t, C.POINTER(_i32), C.POINTER(_i32)],
+    "se_map_area_threshold": [_P, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_uint8, _P, _P],
+    "se_map_from_jpeg": [C.c_char_p, C.c_size_t, _i32, _i32, _P],
+    "se_host_create": [C.POINTER(_P), _i32, _i32, _P, _i32, _P, _P, _P, _P],
+    "se_host_set_ports": [_P, _i32, _P, _P, _P, _P],
+    "se_host_step_replay": [_P, _i64, _P, _P, _P, _P, _P],
+    "se_host_reset_to": [_P, _i64, _P, _P, _P, _P],
+    "se_host_destroy": [_P],
+    "se_host_alloc": [C.c_size_t, C.POINTER(_P)],
+    "se_host_free": [_P],
+    "se_server_create": [C.POINTER(_P), _P, _P],
+    "se_server_call": [_P, _i32],
+    "se_server_launches": [_P, C.POINTER(C.c_uint64)],
+    "se_server_destroy": [_P],
+    "se_destroy": [_P],
+    "se_last_error": [],
+    "se_abi_version": [],
+}
+_RESTYPES = {"se_last_error": C.c_char_p, "se_qtrain_grad_size": _i64}
+EXPORTS = tuple(SIGNATURES)
+
+
+def _ptr(t):
+    """A device tensor's address as a ctypes argument (None: a null pointer)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 def _declare(lib):
-    P, i32, i64, u32, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
-    sig = {
-        "se_create": [C.POINTER(P), C.c_int, i64, i64, i32, i32, P, i32, P, P, P, P, u64, u32],
-        "se_set_ports": [P, i32, P, P, P, P],
-        "se_bind": [P, C.POINTER(SeState)],
-        "se_reset": [P, P, P],
-        "se_reset_to": [P, P, P, P, P],
-        "se_step": [P, P, P],
-        "se_step_seq": [P, P, i64, i32, P],
-        "se_step_seq_mark": [P, P, i64, i32, P, P, i32],
-        "se_step_typed": [P, P, P, P, P],
-        "se_step_replay": [P, P, P, P, P, P],
-        "se_step_agent_replay": [P, P, P, P],
-        "se_observe": [P, P, i64, P],
-        "se_valid_mask": [P, P, P],
-        "se_gen_actions": [P, P, u32, P],
-        "se_sample_actions": [P, P, P, P, u32, P],
-        "se_rollout": [P, P, i64, i32, i32, i64, P, P, P, P],
-        "se_rollout_plan": [P, P, i64, P, P, P, i64, i32, P, P, i64, P, P, P, C.POINTER(SePlanOut), P],
-        "se_mcts_create": [C.POINTER(P), P, i32],
-        "se_mcts_choose": [P, i32, C.c_double, i32, i32, i64, P, P, P, P, P, P, P],
-        "se_mcts_destroy": [P],
-        "se_sarsa_create": [C.POINTER(P), P, i64],
-        "se_sarsa_layout": [P, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)],
-        "se_sarsa_bind": [P, P, C.POINTER(SeSarsaState)],
-        "se_sarsa_step": [P, C.c_double, C.c_double, C.c_double, i32, i32, i32, u32, P, P, P, P, P, P],
-        "se_sarsa_choose": [P, C.c_double, u32, P, P, P, P],
-        "se_sarsa_destroy": [P],
-        "se_qnet_create": [C.POINTER(P), P],
-        "se_qnet_set_weights": [P, P, P, P, P, P, P, P],
-        "se_policy": [P, P, C.c_double, u32, P, i64, P],
-        "se_policy_f32": [P, P, C.c_double, u32, P, i64, P],
-        "se_qnet_repack": [P, P, P],
-        "se_policy_record": [P, P, P, C.c_double, u32, P],
-        "se_policy_record_f32": [P, P, P, C.c_double, u32, P],
-        "se_qnet_destroy": [P],
-        "se_replay_create": [P, P, i64],
-        "se_replay_begin": [P, P, P],
-        "se_replay_end": [P, P, C.c_int32, P],
-        "se_replay_end_reset": [P, P, C.c_int32, P],
-        "se_step_record": [P, P, P, C.c_int32, P],
-        "se_replay_size": [P, P, P],
-        "se_replay_sample": [P, i64, P, u32, P, P, P, P, P, P, P],
-        "se_replay_destroy": [P],
-        "se_qtrain_create": [P, P, i64],
-        "se_qtrain_bind": [P, P, P, P, P, P],
-        "se_qtrain_pack": [P, C.c_int32, P],
-        "se_qtrain_step": [P, i64, P, P, P, P, P, P] + [C.c_float] * 5 + [P, P, P],
-        "se_qtrain_step_policy": [P, P, i64, P, P, P, P, P, P] + [C.c_float] * 5 + [P, P, P],
-        "se_qtrain_step_replay": [P, P, P, i64] + [C.c_float] * 5 + [P, i64, P, P],
-        "se_qtrain_grad_size": [P],
-        "se_qtrain_grad": [P, i64, P, P, P, P, P, P, C.c_float, P, P],
-        "se_qtrain_apply": [P, P, P] + [C.c_float] * 4 + [P, P, P],
-        "se_qtrain_destroy": [P],
-        "se_episode_stats": [P, P, P],
-        "se_clear_stats": [P, P],
-        "se_done_layout": [P, C.POINTER(i64), C.POINTER(i32)],
-        "se_done_list": [P, C.POINTER(i64), C.POINTER(i64)],
-        "se_done_compact": [P, P, P, P],
-        "se_get_counters": [P, C.POINTER(u64), C.POINTER(u64)],
-        "se_set_counters": [P, u64, u64],
-        "se_map_decode_luma": [C.c_char_p, C.c_size_t, P, C.c_size_t, C.POINTER(i32), C.POINTER(i32)],
-        "se_map_area_threshold": [P, i32, i32, i32, i32, i32, i32, i32, i32, C.c_uint8, P, P],
-        "se_map_from_jpeg": [C.c_char_p, C.c_size_t, i32, i32, P],
-        "se_host_create": [C.POINTER(P), i32, i32, P, i32, P, P, P, P],
-        "se_host_set_ports": [P, i32, P, P, P, P],
-        "se_host_step_replay": [P, i64, P, P, P, P, P],
-        "se_host_reset_to": [P, i64, P, P, P, P],
-        "se_host_destroy": [P],
-        "se_host_alloc": [C.c_size_t, C.POINTER(P)],
-        "se_host_free": [P],
-        "se_server_create": [C.POINTER(P), P, P],
-        "se_server_call": [P, i32],
-        "se_server_launches": [P, C.POINTER(C.c_uint64)],
-        "se_server_destroy": [P],
-        "se_destroy": [P],
-        "se_last_error": [],
-        "se_abi_version": [],
-    }
-    for name, args in sig.items():
+    for name, args in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = args
-        fn.restype = C.c_int
-    lib.se_last_error.restype = C.c_char_p
-    lib.se_qtrain_grad_size.restype = i64
+        fn.restype = _RESTYPES.get(name, C.c_int)
 
 
 def lib():

@@ -7,7 +7,7 @@
 // stand-alone header. Uses world.h (WorldDims, LdsWorld, stage_world, sqrt_rn), env_core.h
 // (Ship, Pending, env_key), rollout.h (sample_action, drawn_step, rollout_run), philox.h, and
 // the host side's se_env, check_ready, fail, HIP_TRY, DeviceGuard, aligned16,
-// allow_dynamic_lds and lds_bytes.
+// device_free and world_lds (host.h).
 //
 // One lane runs choose_action for one env: S = num_simulations sequential simulations
 // (selection by UCB1, one expansion, a random rollout, backpropagation) on a private Ship
@@ -319,9 +319,7 @@ int se_mcts_create(se_mcts** out, se_env* env, int32_t max_simulations) {
     // a 16-byte record (node word, action index, visits) and total_reward (8) per node and env
     if (e == hipSuccess && m->n > 0) e = hipMalloc(&m->d_tree, (size_t)(max_simulations + 1) * (size_t)m->n * 24);
     if (e != hipSuccess) {
-        if (m->d_log) (void)hipFree(m->d_log);
-        if (m->d_tree) (void)hipFree(m->d_tree);
-        delete m;
+        se_mcts_destroy(m);
         return fail(SE_EHIP, std::string("se_mcts_create: ") + hipGetErrorString(e));
     }
     *out = m;
@@ -352,13 +350,9 @@ int se_mcts_choose(se_mcts* m, int32_t simulations, double c_param, int32_t max_
         !aligned16(tree_count))
         return fail(SE_EINVAL, "outputs must be 16-byte aligned");
     DeviceGuard g(env->device);
-    const size_t lds = lds_bytes(env);
-    if (lds > 160 * 1024) return fail(SE_EINVAL, "the world image exceeds the LDS");
-    if (lds > 64 * 1024) {
-        static std::atomic<uint64_t> lds_set{0};
-        rc = allow_dynamic_lds(lds_set, reinterpret_cast<const void*>(mcts_kernel), 160 * 1024, env->device);
-        if (rc) return rc;
-    }
+    size_t lds;
+    rc = world_lds<mcts_kernel>(env, lds);
+    if (rc) return rc;
     const size_t nodes = (size_t)(m->max_sims + 1) * (size_t)m->n;
     MctsArgs A{};
     A.world = env->d_world;
@@ -390,10 +384,9 @@ int se_mcts_choose(se_mcts* m, int32_t simulations, double c_param, int32_t max_
 int se_mcts_destroy(se_mcts* m) {
     if (!m) return SE_OK;
     DeviceGuard g(m->device);
-    if (m->d_log) HIP_TRY(hipFree(m->d_log));
-    if (m->d_tree) HIP_TRY(hipFree(m->d_tree));
+    const hipError_t e = device_free({m->d_log, m->d_tree});
     delete m;
-    return SE_OK;
+    return e == hipSuccess ? SE_OK : fail(SE_EHIP, std::string("hipFree: ") + hipGetErrorString(e));
 }
 
 }  // extern "C"

@@ -1,12 +1,13 @@
 #pragma once
 // qpolicy.h — the DQN policy step fused on MFMA: the
 // network handle se_qnet with its packed weights (QnetDims), the policy kernels,
-// launch_policy / launch_policy_f32 and the se_qnet_* / se_policy_* entry points.
+// policy_call with launch_policy / launch_policy_x3, and the se_qnet_* / se_policy_* entry points.
 //
 // A fragment of shipenv.hip's translation unit, included at its end after the host
 // side: not a stand-alone header. Uses world.h (WorldDims, LdsWorld, stage_world,
 // world_view), env_core.h (env_key), philox.h, and the host side's se_env,
-// check_ready, fail, HIP_TRY, DeviceGuard, allow_dynamic_lds, lds_bytes and kBlock.
+// host.h (check_ready, fail, HIP_TRY, DeviceGuard, device_reserve, device_free, allow_lds,
+// lds_bytes) and kBlock.
 //
 // Reference: agents/dqn.py DQNNetwork
 // (:21-33: fc1 6+4P -> 128, relu, fc2 128 -> 128, relu, fc3 128 -> A = 4+P+250)
@@ -1600,21 +1601,23 @@ __global__ __launch_bounds__(kPolicyX3Block) void policy_x3_kernel(PolicyArgs A,
 struct se_qnet {
     se_env* env = nullptr;  // must outlive the qnet (destroy the qnet first)
     int device = 0;
+    int cus = 256;  // the device's compute units (se_qnet_create): the policy kernels' resident workgroups
     QnetDims q{}, qc{};  // the full layout (q_out) and the compact one, whose image follows
     const float* w[6] = {};  // the device weights of the last se_qnet_set_weights (se_qnet_repack)
     size_t c_off = 0;    // byte offset of the compact image
     uint8_t* d_img = nullptr;
-    int img_bytes = 0;
+    size_t img_bytes = 0;
     uint64_t world_version = 0;
     bool packed = false;
     uint8_t* d_img32 = nullptr;  // se_policy_f32's split image (the full layout's fc3, global)
-    int img32_bytes = 0;
+    size_t img32_bytes = 0;
     // the visiting order's scratch list (order_chunk): used when n >= order_min_envs, resolved once
     // by se_qnet_create (SHIPENV_POLICY_ORDER: 0 never, 1 always; unset: from 2^16 envs; 2 always,
     // with the bf16 kernel's list in this global scratch as when it does not fit the LDS, which
     // otherwise happens only past ~10M envs)
     uint32_t* d_order = nullptr;
-    int64_t order_cap = 0, order_min_envs = (int64_t)1 << 16;
+    size_t order_bytes = 0;
+    int64_t order_min_envs = (int64_t)1 << 16;
     bool order_lds = true;
 };
 
@@ -1628,6 +1631,8 @@ int se_qnet_create(se_qnet** out, se_env* env) {
     se_qnet* qn = new se_qnet;
     qn->env = env;
     qn->device = env->device;
+    if (hipDeviceGetAttribute(&qn->cus, hipDeviceAttributeMultiprocessorCount, env->device) != hipSuccess)
+        qn->cus = 256;
     if (const char* v = getenv("SHIPENV_POLICY_ORDER")) {
         qn->order_min_envs = atoi(v) != 0 ? 0 : INT64_MAX;
         qn->order_lds = atoi(v) != 2;
@@ -1647,13 +1652,8 @@ int se_qnet_set_weights(se_qnet* qn, const float* w1, const float* b1, const flo
     const QnetDims q = qnet_dims(env->dims.P);
     const QnetDims qc = qnet_dims(env->dims.P, true, env->cmax, env->fmax);
     const size_t c_off = ((size_t)q.bytes() + 255) & ~(size_t)255;
-    const int total = (int)(c_off + (size_t)qc.bytes());
-    if (total > qn->img_bytes) {
-        if (qn->d_img) HIP_TRY(hipFree(qn->d_img));
-        qn->d_img = nullptr;
-        HIP_TRY(hipMalloc(&qn->d_img, (size_t)total));
-        qn->img_bytes = total;
-    }
+    const int rc = device_reserve(qn->d_img, qn->img_bytes, c_off + (size_t)qc.bytes());
+    if (rc) return rc;
     qn->q = q;
     qn->qc = qc;
     qn->c_off = c_off;
@@ -1675,18 +1675,12 @@ namespace {
 // it, and the scratch list (A.order, A.chunk); position order below order_min_envs
 int policy_order(se_qnet* qn, int* grid, PolicyArgs& A) {
     se_env* env = qn->env;
-    A.order = nullptr;
-    A.chunk = 0;
     if (env->n < qn->order_min_envs) return SE_OK;
     const int64_t per = (env->n + *grid - 1) / *grid;
     const int64_t chunk = (per + 31) & ~(int64_t)31;
     const int64_t g = (env->n + chunk - 1) / chunk;
-    if (g * chunk > qn->order_cap) {
-        if (qn->d_order) HIP_TRY(hipFree(qn->d_order));
-        qn->d_order = nullptr;
-        HIP_TRY(hipMalloc(&qn->d_order, (size_t)(g * chunk) * sizeof(uint32_t)));
-        qn->order_cap = g * chunk;
-    }
+    const int rc = device_reserve(qn->d_order, qn->order_bytes, (size_t)(g * chunk) * sizeof(uint32_t));
+    if (rc) return rc;
     *grid = (int)g;
     A.order = qn->d_order;
     A.chunk = chunk;
@@ -1700,135 +1694,110 @@ struct PolicyRecord {
     int64_t head, cap;
 };
 
-int launch_policy(se_qnet* qn, int32_t* actions, double epsilon, uint32_t t, float* q_out, int64_t ldq,
-                  const PolicyRecord* rec, void* stream) {
-    if (!qn) return fail(SE_EINVAL, "null qnet");
-    se_env* env = qn->env;
-    int rc = check_ready(env);
-    if (rc) return rc;
-    if (!qn->packed) return fail(SE_ESTATE, "se_qnet_set_weights has not been called");
-    if (qn->world_version != env->world_version)
-        return fail(SE_ESTATE, "ports changed since se_qnet_set_weights (the port block is folded into fc1)");
-    if (!actions && env->n > 0) return fail(SE_EINVAL, "null actions");
-    if (q_out && ldq < qn->q.A) return fail(SE_EINVAL, "ldq < number of actions");
-    if (!(epsilon >= 0.0)) return fail(SE_EINVAL, "epsilon must be >= 0");
-    if (env->n == 0) return SE_OK;
-    DeviceGuard g(env->device);
-    // the compact layout unless every row's Q is wanted
-    const QnetDims& q = q_out ? qn->q : qn->qc;
-    size_t lds = (((size_t)q.bytes() + lds_bytes(env) + 7) & ~(size_t)7) + kOrderScanBytes;
-    static std::atomic<uint64_t> lds_set{0};
-    static std::atomic<uint64_t> lds_set_q{0};
-    rc = allow_dynamic_lds(lds_set, reinterpret_cast<const void*>(policy_kernel<false>), 160 * 1024, env->device);
-    if (!rc) rc = allow_dynamic_lds(lds_set_q, reinterpret_cast<const void*>(policy_kernel<true>), 160 * 1024, env->device);
-    if (rc) return rc;
-    if (lds > 160 * 1024) return fail(SE_EINVAL, "network + world image exceed the 160 KB LDS");
-    int dev_cus = 256;
-    if (hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, env->device) != hipSuccess)
-        dev_cus = 256;
-    const int64_t tiles = (env->n + 31) / 32;
-    const int64_t want = (tiles + kPolicyWaves - 1) / kPolicyWaves;
-    const int64_t resident = (int64_t)dev_cus * kPolicyWgPerCu;  // workgroups resident at once
-    int grid = (int)(want < resident ? want : resident);
+// one policy call's arguments, as se_policy / se_policy_f32 take them, and the ring slots of
+// se_policy_record (null: no record)
+struct PolicyCall {
+    int32_t* actions;
+    double epsilon;
+    uint32_t t;
+    float* q_out;
+    int64_t ldq;
+    const PolicyRecord* rec;
+    void* stream;
+};
+
+// What the two datapaths' launches share: everything but the visiting order (policy_order) and
+// lds_list. q is the layout of the image at img.
+PolicyArgs policy_args(const se_qnet* qn, const QnetDims& q, const uint8_t* img, const PolicyCall& c) {
+    const se_env* env = qn->env;
     PolicyArgs A{};
-    rc = policy_order(qn, &grid, A);
-    if (rc) return rc;
-    A.lds_list = -1;
-    if (A.order && qn->order_lds && A.chunk <= 0xffff && lds + (size_t)A.chunk * 2 <= 160 * 1024) {  // the list in LDS
-        A.lds_list = (int32_t)lds;
-        lds += (size_t)A.chunk * 2;
-    }
     A.world = env->d_world;
     A.dims = env->dims;
-    A.qimg = reinterpret_cast<const uint4*>(qn->d_img + (q_out ? 0 : qn->c_off));
+    A.qimg = reinterpret_cast<const uint4*>(img);
     A.q = q;
     A.n = env->n;
     A.env_base = env->env_base;
     A.seed = env->seed;
-    A.t = t;
-    A.eps = epsilon;
+    A.t = c.t;
+    A.eps = c.epsilon;
     A.st = env->st;
-    A.actions = actions;
-    A.q_out = q_out;
-    A.ldq = ldq;
-    if (rec) {
-        A.rec_pos = rec->pos;
-        A.rec_fuel = rec->fuel;
-        A.rec_act = rec->act;
-        A.rec_head = rec->head;
-        A.rec_cap = rec->cap;
+    A.actions = c.actions;
+    A.q_out = c.q_out;
+    A.ldq = c.ldq;
+    if (c.rec) {
+        A.rec_pos = c.rec->pos;
+        A.rec_fuel = c.rec->fuel;
+        A.rec_act = c.rec->act;
+        A.rec_head = c.rec->head;
+        A.rec_cap = c.rec->cap;
     }
-    if (q_out) {
-        policy_kernel<true><<<grid, kPolicyBlock, lds, (hipStream_t)stream>>>(A);
+    return A;
+}
+
+// the bf16 datapath (policy_kernel); policy_call checked the arguments
+int launch_policy(se_qnet* qn, const PolicyCall& c) {
+    se_env* env = qn->env;
+    // the compact layout unless every row's Q is wanted
+    const QnetDims& q = c.q_out ? qn->q : qn->qc;
+    size_t lds = (((size_t)q.bytes() + lds_bytes(env) + 7) & ~(size_t)7) + kOrderScanBytes;
+    int rc = allow_lds<policy_kernel<false>>(kLdsMax, env->device);
+    if (!rc) rc = allow_lds<policy_kernel<true>>(kLdsMax, env->device);
+    if (rc) return rc;
+    if (lds > kLdsMax) return fail(SE_EINVAL, "network + world image exceed the 160 KB LDS");
+    const int64_t tiles = (env->n + 31) / 32;
+    const int64_t want = (tiles + kPolicyWaves - 1) / kPolicyWaves;
+    const int64_t resident = (int64_t)qn->cus * kPolicyWgPerCu;  // workgroups resident at once
+    int grid = (int)(want < resident ? want : resident);
+    PolicyArgs A = policy_args(qn, q, qn->d_img + (c.q_out ? 0 : qn->c_off), c);
+    rc = policy_order(qn, &grid, A);
+    if (rc) return rc;
+    A.lds_list = -1;
+    if (A.order && qn->order_lds && A.chunk <= 0xffff && lds + (size_t)A.chunk * 2 <= kLdsMax) {  // the list in LDS
+        A.lds_list = (int32_t)lds;
+        lds += (size_t)A.chunk * 2;
+    }
+    if (c.q_out) {
+        policy_kernel<true><<<grid, kPolicyBlock, lds, (hipStream_t)c.stream>>>(A);
     } else {
-        policy_kernel<false><<<grid, kPolicyBlock, lds, (hipStream_t)stream>>>(A);
+        policy_kernel<false><<<grid, kPolicyBlock, lds, (hipStream_t)c.stream>>>(A);
     }
     HIP_TRY(hipGetLastError());
     return SE_OK;
 }
-// the split-bf16 datapath (policy_x3_kernel); the caller checked the arguments
-int launch_policy_x3(se_qnet* qn, int32_t* actions, double epsilon, uint32_t t, float* q_out, int64_t ldq,
-                     const PolicyRecord* rec, void* stream) {
+
+// the split-bf16 datapath (policy_x3_kernel); policy_call checked the arguments
+int launch_policy_x3(se_qnet* qn, const PolicyCall& c) {
     se_env* env = qn->env;
     QnetX3Dims d;
-    d.q = q_out ? qn->q : qn->qc;  // the compact rows unless every row's Q is wanted
+    d.q = c.q_out ? qn->q : qn->qc;  // the compact rows unless every row's Q is wanted
     // a zero row of fc3's last tile (row 32 mt3 - 1, past the layout's rows), or none
     d.zrow = d.q.rows < 32 * d.q.mt3 ? (d.q.mt3 - 1) * 8 * 192 + 31 : -1;
-    if (d.bytes() > qn->img32_bytes) {
-        if (qn->d_img32) HIP_TRY(hipFree(qn->d_img32));
-        qn->d_img32 = nullptr;
-        HIP_TRY(hipMalloc(&qn->d_img32, (size_t)d.bytes()));
-        qn->img32_bytes = d.bytes();
-    }
-    const hipStream_t s = (hipStream_t)stream;
+    int rc = device_reserve(qn->d_img32, qn->img32_bytes, (size_t)d.bytes());
+    if (rc) return rc;
+    const hipStream_t s = (hipStream_t)c.stream;
     // the image from the current weights (in place updates by an optimizer or T2 included)
     PackX3Args pk{qn->w[0], qn->w[1], qn->w[2], qn->w[3], qn->w[4], qn->w[5], env->d_world, env->dims, d,
                   qn->d_img32};
     constexpr int kPtabBytes = kX3PtabBytes;
-    const bool w3_global = d.bytes() + kPtabBytes + kOrderScanBytes > 160 * 1024;
+    const bool w3_global = (size_t)(d.bytes() + kPtabBytes + kOrderScanBytes) > kLdsMax;
     if (w3_global) {  // fc3's fragments are read from a packed global image
         qnet_pack_x3_kernel<<<128, 256, 0, s>>>(pk);
         HIP_TRY(hipGetLastError());
     }
     const size_t lds = (size_t)(w3_global ? ((d.w3() + 7) & ~7) : ((d.bytes() + 15) & ~15) + kPtabBytes) +
                        kOrderScanBytes;
-    if (lds > 160 * 1024) return fail(SE_EINVAL, "split-bf16 network exceeds the 160 KB LDS");
-    static std::atomic<uint64_t> lds_set0{0}, lds_set1{0};
-    static std::atomic<uint64_t> lds_set2{0};
-    int rc = allow_dynamic_lds(lds_set0, reinterpret_cast<const void*>(policy_x3_kernel<false>), 160 * 1024, env->device);
-    if (!rc) rc = allow_dynamic_lds(lds_set1, reinterpret_cast<const void*>(policy_x3_kernel<true>), 160 * 1024, env->device);
-    if (!rc) rc = allow_dynamic_lds(lds_set2, reinterpret_cast<const void*>(policy_x3_kernel<true, true>), 160 * 1024, env->device);
+    if (lds > kLdsMax) return fail(SE_EINVAL, "split-bf16 network exceeds the 160 KB LDS");
+    rc = allow_lds<policy_x3_kernel<false>>(kLdsMax, env->device);
+    if (!rc) rc = allow_lds<policy_x3_kernel<true>>(kLdsMax, env->device);
+    if (!rc) rc = allow_lds<policy_x3_kernel<true, true>>(kLdsMax, env->device);
     if (rc) return rc;
-    int dev_cus = 256;
-    if (hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, env->device) != hipSuccess)
-        dev_cus = 256;
     const int64_t tiles = (env->n + 31) / 32;
     const int64_t want = (tiles + kPolicyX3Waves - 1) / kPolicyX3Waves;
-    int grid = (int)(want < dev_cus ? want : dev_cus);
-    PolicyArgs A{};
+    int grid = (int)(want < qn->cus ? want : qn->cus);
+    PolicyArgs A = policy_args(qn, d.q, qn->d_img32, c);
     rc = policy_order(qn, &grid, A);
     if (rc) return rc;
-    A.world = env->d_world;
-    A.dims = env->dims;
-    A.qimg = reinterpret_cast<const uint4*>(qn->d_img32);
-    A.q = d.q;
-    A.n = env->n;
-    A.env_base = env->env_base;
-    A.seed = env->seed;
-    A.t = t;
-    A.eps = epsilon;
-    A.st = env->st;
-    A.actions = actions;
-    A.q_out = q_out;
-    A.ldq = ldq;
-    if (rec) {
-        A.rec_pos = rec->pos;
-        A.rec_fuel = rec->fuel;
-        A.rec_act = rec->act;
-        A.rec_head = rec->head;
-        A.rec_cap = rec->cap;
-    }
-    if (q_out) {  // the full layout (fc3 from global memory): unmasked Q rows for q_out
+    if (c.q_out) {  // the full layout (fc3 from global memory): unmasked Q rows for q_out
         if (!w3_global) return fail(SE_EINVAL, "q_out: the full fc3 layout is expected in global memory");
         policy_x3_kernel<true, true><<<grid, kPolicyX3Block, lds, s>>>(A, d, pk);
     } else if (w3_global) {
@@ -1840,8 +1809,9 @@ int launch_policy_x3(se_qnet* qn, int32_t* actions, double epsilon, uint32_t t, 
     return SE_OK;
 }
 
-int launch_policy_f32(se_qnet* qn, int32_t* actions, double epsilon, uint32_t t, float* q_out, int64_t ldq,
-                      const PolicyRecord* rec, void* stream) {
+// One policy call of either precision (launch: launch_policy or launch_policy_x3): the
+// argument checks, in one order whatever the datapath, then the launch on the env's device.
+int policy_call(int (*launch)(se_qnet*, const PolicyCall&), se_qnet* qn, const PolicyCall& c) {
     if (!qn) return fail(SE_EINVAL, "null qnet");
     se_env* env = qn->env;
     int rc = check_ready(env);
@@ -1849,12 +1819,12 @@ int launch_policy_f32(se_qnet* qn, int32_t* actions, double epsilon, uint32_t t,
     if (!qn->packed) return fail(SE_ESTATE, "se_qnet_set_weights has not been called");
     if (qn->world_version != env->world_version)
         return fail(SE_ESTATE, "ports changed since se_qnet_set_weights (the port block is folded into fc1)");
-    if (!actions && env->n > 0) return fail(SE_EINVAL, "null actions");
-    if (q_out && ldq < qn->q.A) return fail(SE_EINVAL, "ldq < number of actions");
-    if (!(epsilon >= 0.0)) return fail(SE_EINVAL, "epsilon must be >= 0");
+    if (!c.actions && env->n > 0) return fail(SE_EINVAL, "null actions");
+    if (c.q_out && c.ldq < qn->q.A) return fail(SE_EINVAL, "ldq < number of actions");
+    if (!(c.epsilon >= 0.0)) return fail(SE_EINVAL, "epsilon must be >= 0");
     if (env->n == 0) return SE_OK;
     DeviceGuard g(env->device);
-    return launch_policy_x3(qn, actions, epsilon, t, q_out, ldq, rec, stream);
+    return launch(qn, c);
 }
 
 }  // namespace
@@ -1863,12 +1833,12 @@ extern "C" {
 
 int se_policy(se_qnet* qn, int32_t* actions, double epsilon, uint32_t t, float* q_out, int64_t ldq,
               void* stream) {
-    return launch_policy(qn, actions, epsilon, t, q_out, ldq, nullptr, stream);
+    return policy_call(launch_policy, qn, {actions, epsilon, t, q_out, ldq, nullptr, stream});
 }
 
 int se_policy_f32(se_qnet* qn, int32_t* actions, double epsilon, uint32_t t, float* q_out, int64_t ldq,
                   void* stream) {
-    return launch_policy_f32(qn, actions, epsilon, t, q_out, ldq, nullptr, stream);
+    return policy_call(launch_policy_x3, qn, {actions, epsilon, t, q_out, ldq, nullptr, stream});
 }
 
 #if SHIPENV_X3_TRACE
@@ -1891,15 +1861,12 @@ int se_qnet_repack(se_qnet* qn, int32_t* bump, void* stream) {
     return SE_OK;
 }
 
-
 int se_qnet_destroy(se_qnet* qn) {
     if (!qn) return SE_OK;
     if (qn->d_img || qn->d_img32 || qn->d_order) {  // does not touch the env, which may be gone already
         DeviceGuard g(qn->device);
         (void)hipDeviceSynchronize();
-        if (qn->d_img) (void)hipFree(qn->d_img);
-        if (qn->d_img32) (void)hipFree(qn->d_img32);
-        if (qn->d_order) (void)hipFree(qn->d_order);
+        (void)device_free({qn->d_img, qn->d_img32, qn->d_order});
     }
     delete qn;
     return SE_OK;

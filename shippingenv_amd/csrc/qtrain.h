@@ -8,7 +8,7 @@
 // env_core.h (env_key), step_io.h (kRecDone), qpolicy.h (se_qnet, QnetDims, the bf16
 // split and MFMA helpers), replay.h (se_replay, Ring, the pick_* sampler, ship_col),
 // and the host side's se_env, check_ready, fail, HIP_TRY, DeviceGuard and
-// allow_dynamic_lds.
+// allow_lds (host.h).
 //
 // Reference: agents/dqn.py DQNAgent.update (:206-245) on a sampled minibatch.
 // It computes q = DQNNetwork(states)[a] and y = r + gamma * max target(next_states) * (1 - done),
@@ -1586,8 +1586,7 @@ int qtrain_step(se_qtrain* q, se_qnet* qn, int64_t batch, const float* obs, cons
     const hipStream_t s = (hipStream_t)stream;
     const int64_t tiles = (batch + kQT - 1) / kQT;
     const size_t lds = (size_t)(16 * kLS + 4 * 128 * kLS + 8 * 32 + 8 * 32) * 4 + (3 * 8 * 3 * 64 * 16 + 32 * 4 + 256);
-    static std::atomic<uint64_t> lds_set{0};
-    rc = allow_dynamic_lds(lds_set, reinterpret_cast<const void*>(qtrain_tile_kernel), (int)lds, q->device);
+    rc = allow_lds<qtrain_tile_kernel>(lds, q->device);
     if (rc) return rc;
     QtStepArgs A{q->W, q->on, q->tg, q->d, batch, obs, next_obs, act, rew, done, weight, gamma,
                  qn && !ring ? step_dev : nullptr, ring ? 1 : 0, ring ? ring->ring : Ring{},
@@ -1661,7 +1660,7 @@ int se_qtrain_destroy(se_qtrain* q) {
     if (q->d_ws) {
         DeviceGuard g(q->device);
         (void)hipDeviceSynchronize();
-        (void)hipFree(q->d_ws);
+        (void)device_free({q->d_ws});
     }
     delete q;
     return SE_OK;

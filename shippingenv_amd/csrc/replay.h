@@ -7,7 +7,7 @@
 // not a stand-alone header. Uses world.h (WorldDims, LdsWorld, world_view),
 // env_core.h (Ship, env_key, reset_ship), step_io.h (the StepRecord contract that
 // step_kernel's record instantiation fills: kRecDone, kRecMaxIters), philox.h,
-// qpolicy.h (se_qnet, PolicyRecord, launch_policy / launch_policy_f32), and the
+// qpolicy.h (se_qnet, PolicyRecord, policy_call, launch_policy / launch_policy_x3), and the
 // host side's se_env, launch_step, check_ready, fail, HIP_TRY, DeviceGuard,
 // aligned16, grid_for and kBlock.
 //
@@ -383,6 +383,21 @@ struct se_replay {
     Ring ring{};
 };
 
+namespace {
+// what every call on a ring checks first: the handle, then its env
+int replay_ready(se_replay* r) {
+    if (!r) return fail(SE_EINVAL, "null replay");
+    return check_ready(r->env);
+}
+
+// the ring once a step's n transitions are complete: new_size is what the kernel was given
+void ring_advance(se_replay* r, int64_t new_size) {
+    r->head = (r->head + r->env->n) % r->cap;
+    r->size = new_size;
+    r->open = false;
+}
+}  // namespace
+
 extern "C" {
 
 int se_replay_create(se_replay** out, se_env* env, int64_t capacity) {
@@ -421,8 +436,7 @@ int se_replay_create(se_replay** out, se_env* env, int64_t capacity) {
 }
 
 int se_replay_begin(se_replay* r, const int32_t* actions, void* stream) {
-    if (!r) return fail(SE_EINVAL, "null replay");
-    int rc = check_ready(r->env);
+    int rc = replay_ready(r);
     if (rc) return rc;
     if (!actions) return fail(SE_EINVAL, "null actions");
     if (r->open) return fail(SE_ESTATE, "se_replay_begin twice without se_replay_end");
@@ -441,8 +455,7 @@ int se_replay_begin(se_replay* r, const int32_t* actions, void* stream) {
 
 namespace {
 int replay_end(se_replay* r, uint8_t* cut, int32_t max_steps, bool reset_cut, void* stream) {
-    if (!r) return fail(SE_EINVAL, "null replay");
-    int rc = check_ready(r->env);
+    int rc = replay_ready(r);
     if (rc) return rc;
     if (!r->open) return fail(SE_ESTATE, "se_replay_end without se_replay_begin");
     se_env* env = r->env;
@@ -461,9 +474,20 @@ int replay_end(se_replay* r, uint8_t* cut, int32_t max_steps, bool reset_cut, vo
         replay_end_kernel<<<grid_for(std::max<int64_t>(env->n, 1)), kBlock, 0, (hipStream_t)stream>>>(A);
     HIP_TRY(hipGetLastError());
     if (reset_cut) env->epoch += 1;  // as se_reset
-    r->head = (r->head + env->n) % r->cap;
-    r->size = new_size;
-    r->open = false;
+    ring_advance(r, new_size);
+    return SE_OK;
+}
+
+// se_policy_record of either precision: the policy call with the ring's slots for (s, a)
+int policy_record(int (*launch)(se_qnet*, const PolicyCall&), se_qnet* qn, se_replay* r, int32_t* actions,
+                  double epsilon, uint32_t t, void* stream) {
+    if (!qn || !r) return fail(SE_EINVAL, "null qnet / replay");
+    if (qn->env != r->env) return fail(SE_EINVAL, "the qnet and the replay belong to different envs");
+    if (r->open) return fail(SE_ESTATE, "se_replay_begin twice without se_replay_end");
+    const PolicyRecord rec{r->ring.s_pos, r->ring.s_fuel, r->ring.act, r->head, r->cap};
+    const int rc = policy_call(launch, qn, {actions, epsilon, t, nullptr, 0, &rec, stream});
+    if (rc) return rc;
+    r->open = true;
     return SE_OK;
 }
 }  // namespace
@@ -479,8 +503,7 @@ int se_replay_end_reset(se_replay* r, uint8_t* cut, int32_t max_steps, void* str
 }
 
 int se_step_record(se_replay* r, const int32_t* actions, uint8_t* cut, int32_t max_steps, void* stream) {
-    if (!r) return fail(SE_EINVAL, "null replay");
-    int rc = check_ready(r->env);
+    int rc = replay_ready(r);
     if (rc) return rc;
     if (!r->open) return fail(SE_ESTATE, "se_step_record without se_replay_begin / se_policy_record");
     if (!cut) return fail(SE_EINVAL, "se_step_record needs a cut buffer");
@@ -502,32 +525,16 @@ int se_step_record(se_replay* r, const int32_t* actions, uint8_t* cut, int32_t m
     rc = launch_step(env, false, false, actions, nullptr, nullptr, nullptr, stream, &rec);
     if (rc) return rc;
     env->epoch += 1;  // as se_reset
-    r->head = (r->head + env->n) % r->cap;
-    r->size = new_size;
-    r->open = false;
+    ring_advance(r, new_size);
     return SE_OK;
 }
 
 int se_policy_record(se_qnet* qn, se_replay* r, int32_t* actions, double epsilon, uint32_t t, void* stream) {
-    if (!qn || !r) return fail(SE_EINVAL, "null qnet / replay");
-    if (qn->env != r->env) return fail(SE_EINVAL, "the qnet and the replay belong to different envs");
-    if (r->open) return fail(SE_ESTATE, "se_replay_begin twice without se_replay_end");
-    const PolicyRecord rec{r->ring.s_pos, r->ring.s_fuel, r->ring.act, r->head, r->cap};
-    const int rc = launch_policy(qn, actions, epsilon, t, nullptr, 0, &rec, stream);
-    if (rc) return rc;
-    r->open = true;
-    return SE_OK;
+    return policy_record(launch_policy, qn, r, actions, epsilon, t, stream);
 }
 
 int se_policy_record_f32(se_qnet* qn, se_replay* r, int32_t* actions, double epsilon, uint32_t t, void* stream) {
-    if (!qn || !r) return fail(SE_EINVAL, "null qnet / replay");
-    if (qn->env != r->env) return fail(SE_EINVAL, "the qnet and the replay belong to different envs");
-    if (r->open) return fail(SE_ESTATE, "se_replay_begin twice without se_replay_end");
-    const PolicyRecord rec{r->ring.s_pos, r->ring.s_fuel, r->ring.act, r->head, r->cap};
-    const int rc = launch_policy_f32(qn, actions, epsilon, t, nullptr, 0, &rec, stream);
-    if (rc) return rc;
-    r->open = true;
-    return SE_OK;
+    return policy_record(launch_policy_x3, qn, r, actions, epsilon, t, stream);
 }
 
 int se_replay_size(se_replay* r, int64_t* size, int64_t* capacity) {
@@ -540,8 +547,7 @@ int se_replay_size(se_replay* r, int64_t* size, int64_t* capacity) {
 int se_replay_sample(se_replay* r, int64_t batch, const uint32_t* t_dev, uint32_t t, float* obs,
                      float* next_obs, int64_t* actions, float* rewards, float* dones, float* weights,
                      void* stream) {
-    if (!r) return fail(SE_EINVAL, "null replay");
-    int rc = check_ready(r->env);
+    int rc = replay_ready(r);
     if (rc) return rc;
     if (batch < 1 || batch > (int64_t(1) << 24)) return fail(SE_EINVAL, "batch must be in [1, 2^24]");
     if (!obs || !next_obs || !actions || !rewards || !dones || !weights)
@@ -561,7 +567,7 @@ int se_replay_destroy(se_replay* r) {
     if (r->d_block) {  // does not touch the env, which may be gone already
         DeviceGuard g(r->device);
         (void)hipDeviceSynchronize();
-        (void)hipFree(r->d_block);
+        (void)device_free({r->d_block});
     }
     delete r;
     return SE_OK;

@@ -6,7 +6,7 @@
 // A fragment of shipenv.hip's translation unit, included at its end after mcts.h: not a
 // stand-alone header. Uses world.h (WorldDims, LdsWorld, stage_world), env_core.h (Ship,
 // Pending, env_key, u32, reset_ship), rollout.h (sample_action, drawn_step), philox.h, and the
-// host side's se_env, check_ready, fail, HIP_TRY, DeviceGuard, allow_dynamic_lds, lds_bytes
+// host side's se_env, check_ready, fail, HIP_TRY, DeviceGuard, device_free, world_lds (host.h)
 // and grid_for.
 //
 // One vector step runs the body of train's inner loop (:255-272) for every env:
@@ -352,14 +352,6 @@ int sarsa_ready(se_sarsa* h, bool need_bind) {
     return SE_OK;
 }
 
-template <typename Kernel>
-int sarsa_lds(se_env* env, Kernel kernel, std::atomic<uint64_t>& lds_set, size_t& lds) {
-    lds = lds_bytes(env);
-    if (lds > 160 * 1024) return fail(SE_EINVAL, "the world image exceeds the LDS");
-    if (lds > 64 * 1024) return allow_dynamic_lds(lds_set, reinterpret_cast<const void*>(kernel), 160 * 1024, env->device);
-    return SE_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -403,10 +395,7 @@ int se_sarsa_create(se_sarsa** out, se_env* env, int64_t max_table_bytes) {
     }
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        if (h->d_owner) (void)hipFree(h->d_owner);
-        if (h->d_park_entry) (void)hipFree(h->d_park_entry);
-        if (h->d_park_val) (void)hipFree(h->d_park_val);
-        delete h;
+        se_sarsa_destroy(h);
         return fail(SE_EHIP, std::string("se_sarsa_create: ") + hipGetErrorString(e));
     }
     *out = h;
@@ -445,9 +434,8 @@ int se_sarsa_step(se_sarsa* h, double lr, double gamma, double epsilon, int32_t 
     if (env->n == 0) return SE_OK;
     if (!reward || !ended || !status || !fin_return || !fin_len) return fail(SE_EINVAL, "null output pointer");
     DeviceGuard g(env->device);
-    static std::atomic<uint64_t> lds_set{0};
     size_t lds;
-    rc = sarsa_lds(env, sarsa_step_kernel, lds_set, lds);
+    rc = world_lds<sarsa_step_kernel>(env, lds);
     if (rc) return rc;
     SarsaArgs A{};
     A.world = env->d_world;
@@ -494,9 +482,8 @@ int se_sarsa_choose(se_sarsa* h, double epsilon, uint32_t t, int32_t* type, int3
     if (env->n == 0) return SE_OK;
     if (!type || !a || !b) return fail(SE_EINVAL, "null output pointer");
     DeviceGuard g(env->device);
-    static std::atomic<uint64_t> lds_set{0};
     size_t lds;
-    rc = sarsa_lds(env, sarsa_choose_kernel, lds_set, lds);
+    rc = world_lds<sarsa_choose_kernel>(env, lds);
     if (rc) return rc;
     const SarsaChooseArgs A{env->d_world, env->dims, env->n, env->env_base, env->seed, t, env->st,
                             h->q, h->A, h->cmax, epsilon, type, a, b};
@@ -508,11 +495,9 @@ int se_sarsa_choose(se_sarsa* h, double epsilon, uint32_t t, int32_t* type, int3
 int se_sarsa_destroy(se_sarsa* h) {
     if (!h) return SE_OK;
     DeviceGuard g(h->device);
-    if (h->d_owner) HIP_TRY(hipFree(h->d_owner));
-    if (h->d_park_entry) HIP_TRY(hipFree(h->d_park_entry));
-    if (h->d_park_val) HIP_TRY(hipFree(h->d_park_val));
+    const hipError_t e = device_free({h->d_owner, h->d_park_entry, h->d_park_val});
     delete h;
-    return SE_OK;
+    return e == hipSuccess ? SE_OK : fail(SE_EHIP, std::string("hipFree: ") + hipGetErrorString(e));
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 // A fragment of shipenv.hip's translation unit, included at its end after qtrain.h: not a
 // stand-alone header. Uses world.h (WorldDims, LdsWorld, stage_world), env_core.h (Ship,
 // Pending, replay_env), shipenv.hip's kFuelInit, and the host side's se_env, fail, HIP_TRY,
-// DeviceGuard, allow_dynamic_lds and lds_bytes.
+// DeviceGuard, allow_lds and lds_bytes (host.h).
 //
 // Reference callers: the agents
 // step one env at a time, once per decision (agents/dqn.py:287) and ~500 times per MCTS
@@ -142,8 +142,7 @@ void host_store(uint32_t* p, uint32_t v) { __atomic_store_n(p, v, __ATOMIC_RELEA
 // (re)launch the wave once the previous one has ended
 int server_launch(se_server* s) {
     if (s->launched) HIP_TRY(hipStreamSynchronize(s->stream));  // returns once it has ended
-    static std::atomic<uint64_t> lds_set{0};
-    int rc = allow_dynamic_lds(lds_set, reinterpret_cast<const void*>(server_kernel), 160 * 1024, s->device);
+    int rc = allow_lds<server_kernel>(kLdsMax, s->device);
     if (rc) return rc;
     host_store(&s->blk->running, 1u);
     server_kernel<<<1, 64, lds_bytes(s->env) + sizeof(se_server_block), s->stream>>>(s->args);
@@ -218,7 +217,7 @@ int se_server_create(se_server** out, se_env* env, se_server_block* blk) {
     if (!blk) return fail(SE_EINVAL, "null block");
     if (reinterpret_cast<uintptr_t>(blk) & 63) return fail(SE_EINVAL, "the block must be 64-byte aligned");
     if (!host_pinned(blk)) return fail(SE_EINVAL, "the block must be pinned host memory (se_host_alloc)");
-    if (lds_bytes(env) + sizeof(se_server_block) > 160 * 1024) return fail(SE_EINVAL, "the world image exceeds the LDS");
+    if (lds_bytes(env) + sizeof(se_server_block) > kLdsMax) return fail(SE_EINVAL, "the world image exceeds the LDS");
     DeviceGuard g(env->device);
     se_server* s = new se_server;
     s->env = env;

@@ -29,6 +29,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -89,7 +90,7 @@ struct se_env {
     uint32_t* d_world = nullptr;
     int64_t seg = 0;    // done-list segment stride (records per wave-iteration: 256)
     int64_t iters = 1;  // groups per thread of the step kernel
-    int world_cap = 0;  // words allocated
+    size_t world_cap = 0;  // bytes allocated
     uint64_t world_version = 0;  // bumped by every world upload (se_qnet folds the ports)
     int32_t cmax = 0, fmax = 0;  // largest TAKE_CARGO / TAKE_FUEL amount any port allows (se_qnet)
     int32_t stock_cargo_max = 0;  // largest port_cargo (se_sarsa: sample_action takes up to the whole stock)
@@ -122,48 +123,7 @@ struct se_host {
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return fail(SE_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));        \
-    } while (0)
-
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: `done` holds, for one
-// kernel, a bit per device it has been set on (devices >= 64 set it on every call).
-int allow_dynamic_lds(std::atomic<uint64_t>& done, const void* kernel, int bytes, int device) {
-    const uint64_t bit = device >= 0 && device < 64 ? 1ull << device : 0ull;
-    if (bit && (done.load(std::memory_order_acquire) & bit)) return SE_OK;
-    HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    done.fetch_or(bit, std::memory_order_acq_rel);
-    return SE_OK;
-}
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-int grid_for(int64_t items, int cap = kMaxBlocks) {
-    int64_t b = (items + kBlock - 1) / kBlock;
-    if (b < 1) b = 1;
-    if (b > cap) b = cap;
-    return (int)b;
-}
+#include "host.h"  // fail, HIP_TRY, DeviceGuard, device blocks, the LDS opt-in, check_ready
 
 // ---------------------------------------------------------------- launch-time switches
 // SHIPENV_STEP_BLOCKS, _DONE_PAD, _NT_LOADS, _SEQ_MAX_STEPS, _SEQ_FUSE, _SEQ_GATE_POOL and
@@ -238,8 +198,6 @@ bool mask_tiled() {
     return v && atoi(v) != 0;
 }
 
-size_t lds_bytes(const se_env* env) { return (size_t)env->dims.padded() * 4; }
-
 // The world image (layout above WorldDims, world.h) of an H x W map and P ports, built on the
 // host: uploaded by se_create / se_set_ports, kept as is by the host handles.
 int build_world_image(int H, int W, const std::vector<uint8_t>& water, int32_t P, const int32_t* px,
@@ -303,12 +261,8 @@ int upload_world(se_env* env, int32_t P, const int32_t* px, const int32_t* py, c
     std::vector<uint32_t> img;
     int rc = build_world_image(env->dims.H, env->dims.W, env->water, P, px, py, pf, pc, d, img);
     if (rc) return rc;
-    if (d.padded() > env->world_cap) {
-        if (env->d_world) HIP_TRY(hipFree(env->d_world));
-        env->d_world = nullptr;
-        HIP_TRY(hipMalloc(&env->d_world, (size_t)d.padded() * 4));
-        env->world_cap = d.padded();
-    }
+    rc = device_reserve(env->d_world, env->world_cap, (size_t)d.padded() * 4);
+    if (rc) return rc;
     HIP_TRY(hipMemcpy(env->d_world, img.data(), (size_t)d.padded() * 4, hipMemcpyHostToDevice));
     env->dims = d;
     env->cmax = env->fmax = env->stock_cargo_max = 0;
@@ -321,14 +275,6 @@ int upload_world(se_env* env, int32_t P, const int32_t* px, const int32_t* py, c
     env->mask_ntmpl = 1 + P;  // se_valid_mask's row templates (mask_tmpl_kernel)
     for (int p = 0; p < P; ++p)
         for (int q = 0; q < P; ++q) env->mask_ntmpl += (px[p] == px[q] && py[p] == py[q]) ? 1 : 0;
-    return SE_OK;
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-int check_ready(se_env* env) {
-    if (!env) return fail(SE_EINVAL, "null env");
-    if (!env->bound) return fail(SE_ESTATE, "se_bind has not been called");
     return SE_OK;
 }
 
@@ -449,7 +395,7 @@ int launch_step_seq(se_env* env, const int32_t* act, int64_t ld, int32_t steps, 
         // the image, then stock_by_code's table, then the waves' GATE pools. A world whose image
         // leaves no room for the pools under the 64 KiB a launch can ask for draws directly.
         const size_t base = lds_bytes(env) + kStockByCodeBytes;
-        const bool pool = env->seq_gate_pool && base + kGatePoolBytes <= (size_t)64 * 1024;
+        const bool pool = env->seq_gate_pool && base + kGatePoolBytes <= kLdsDefault;
         const size_t lds = base + (pool ? kGatePoolBytes : 0);
         const auto kernel = pool ? (env->nt_loads ? step_seq_kernel<true, true> : step_seq_kernel<false, true>)
                                  : (env->nt_loads ? step_seq_kernel<true, false> : step_seq_kernel<false, false>);
@@ -618,7 +564,7 @@ int se_step_seq_mark(se_env* env, const int32_t* actions, int64_t ld, int32_t st
     // A world image that fills the 64 KiB a launch can ask for leaves no room for the fused
     // kernel's stock table: such an env steps per launch, as step_kernel still fits.
     const bool fused = env->seq_fuse && env->n > 0 && !(env->flags & SE_FLAG_AUTO_RESET) &&
-                       lds_bytes(env) + kStockByCodeBytes <= (size_t)64 * 1024;
+                       lds_bytes(env) + kStockByCodeBytes <= kLdsDefault;
     for (int32_t k = 0; k <= steps;) {
         if (event && k == mark_after) {
             DeviceGuard g(env->device);
@@ -691,14 +637,9 @@ int se_valid_mask(se_env* env, uint8_t* bits, void* stream) {
     if (aligned16(bits) && env->dims.P <= 64 && env->mask_ntmpl <= kMaskTmplMax && !env->mask_tiled) {
         // the row templates, rebuilt when the world image changed
         const size_t need = (size_t)kMaskHdr + (size_t)env->mask_ntmpl * tb;
-        if (need > env->mask_tmpl_cap) {
-            if (env->d_mask_tmpl) HIP_TRY(hipFree(env->d_mask_tmpl));
-            env->d_mask_tmpl = nullptr;
-            env->mask_tmpl_cap = 0;
-            HIP_TRY(hipMalloc(&env->d_mask_tmpl, need));
-            env->mask_tmpl_cap = need;
-            env->mask_tmpl_version = 0;
-        }
+        if (need > env->mask_tmpl_cap) env->mask_tmpl_version = 0;  // a new block holds no templates
+        rc = device_reserve(env->d_mask_tmpl, env->mask_tmpl_cap, need);
+        if (rc) return rc;
         if (env->mask_tmpl_version != env->world_version) {
             mask_tmpl_kernel<<<1, kBlock, 0, s>>>(env->d_world, env->dims, stride, env->d_mask_tmpl);
             HIP_TRY(hipGetLastError());
@@ -790,14 +731,9 @@ int se_rollout_plan(se_env* env, const int32_t* src, int64_t m, const int32_t* t
     if (m == 0) return SE_OK;
     DeviceGuard g(env->device);
     const bool agent = a == nullptr;
-    const size_t lds = lds_bytes(env);
-    if (lds > 160 * 1024) return fail(SE_EINVAL, "the world image exceeds the LDS");
-    if (lds > 64 * 1024) {  // once per kernel and device: no call on the launch path after the first
-        static std::atomic<uint64_t> lds_typed{0}, lds_agent{0};
-        rc = agent ? allow_dynamic_lds(lds_agent, reinterpret_cast<const void*>(plan_kernel<true>), 160 * 1024, env->device)
-                   : allow_dynamic_lds(lds_typed, reinterpret_cast<const void*>(plan_kernel<false>), 160 * 1024, env->device);
-        if (rc) return rc;
-    }
+    size_t lds;
+    rc = agent ? world_lds<plan_kernel<true>>(env, lds) : world_lds<plan_kernel<false>>(env, lds);
+    if (rc) return rc;
     PlanArgs A{};
     A.world = env->d_world;
     A.dims = env->dims;
@@ -894,10 +830,7 @@ int se_set_counters(se_env* env, uint64_t step, uint64_t epoch) {
 int se_destroy(se_env* env) {
     if (!env) return SE_OK;
     DeviceGuard g(env->device);
-    if (env->d_world) (void)hipFree(env->d_world);
-    if (env->d_slab) (void)hipFree(env->d_slab);
-    if (env->d_offsets) (void)hipFree(env->d_offsets);
-    if (env->d_mask_tmpl) (void)hipFree(env->d_mask_tmpl);
+    (void)device_free({env->d_world, env->d_slab, env->d_offsets, env->d_mask_tmpl});
     delete env;
     return SE_OK;
 }

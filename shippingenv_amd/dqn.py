@@ -35,6 +35,7 @@ import os
 import torch
 
 from . import _native as N
+from ._native import _ptr
 from .policy import HIDDEN, DQNNetwork, QPolicy
 
 # utils/constants.py TrainingDefaults (DQN_*): the reference's defaults
@@ -48,10 +49,6 @@ DQN_LEARNING_RATE = 0.001
 MAX_STEPS_PER_EPISODE = 1000
 
 _DEBUG = os.environ.get("SHIPENV_DEBUG") == "1"
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class MiniBatch:

@@ -13,7 +13,7 @@ from collections import namedtuple
 import torch
 
 from . import _native as N
-from .vec import _ptr
+from ._native import _ptr
 
 # se_mcts_choose statuses (include/shipenv.h SE_MCTS_*)
 OK, CUT, RAISED, NEVER_RETURNS = N.MCTS_OK, N.MCTS_CUT, N.MCTS_RAISED, N.MCTS_NEVER_RETURNS

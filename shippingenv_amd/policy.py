@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as N
+from ._native import _ptr
 
 HIDDEN = 128  # DQNNetwork's hidden_size default (agents/dqn.py:24); the fused kernel's width
 
@@ -34,10 +35,6 @@ class DQNNetwork(nn.Module):
         x = torch.relu(self.fc1(x))
         x = torch.relu(self.fc2(x))
         return self.fc3(x)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
 
 
 class QPolicy:
@@ -68,7 +65,7 @@ class QPolicy:
     def repack(self, bump: torch.Tensor | None = None):
         """Repack the same weight tensors after their values changed in place (an optimizer
         step); bump (device int32 [1]) is advanced by one on the stream (se_qnet_repack)."""
-        N.check(N.lib().se_qnet_repack(self._h, _ptr(bump) if bump is not None else None, self.env._stream()))
+        N.check(N.lib().se_qnet_repack(self._h, _ptr(bump), self.env._stream()))
 
     def act_record(self, replay, epsilon: float = 0.0, t: int = 0, precision: str = "bf16"):
         """act() plus the replay ring's remember(state, action) in the same launch
@@ -95,7 +92,7 @@ class QPolicy:
         fn = N.lib().se_policy if precision == "bf16" else N.lib().se_policy_f32
         ldq = 0 if q_out is None else q_out.stride(0)
         N.check(fn(self._h, _ptr(self.actions), float(epsilon), int(t) & 0xFFFFFFFF,
-                   None if q_out is None else _ptr(q_out), ldq, self.env._stream()))
+                   _ptr(q_out), ldq, self.env._stream()))
         return self.actions
 
     def close(self):

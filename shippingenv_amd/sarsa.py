@@ -15,7 +15,7 @@ import ctypes as C
 import torch
 
 from . import _native as N
-from .vec import _ptr
+from ._native import _ptr
 
 # se_sarsa_step statuses (include/shipenv.h SE_SARSA_*)
 OK, CUT, RAISED, NEVER_RETURNS = N.SARSA_OK, N.SARSA_CUT, N.SARSA_RAISED, N.SARSA_NEVER_RETURNS

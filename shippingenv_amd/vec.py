@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from ._native import _ptr
 from .maps import builtin_water
 
 DEFAULT_PORTS = [[41, 40], [60, 22], [78, 29], [49, 72], [62, 72]]  # utils/constants.py:57-63
@@ -61,10 +62,6 @@ def random_water_ports(water, n_ports, seed):
     cells = np.argwhere(np.asarray(water) != 0)
     pick = rng.choice(len(cells), size=n_ports, replace=False)
     return [[int(a), int(b)] for a, b in cells[np.sort(pick)]]
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 try:  # the current stream's hipStream_t without building a torch Stream object
@@ -127,11 +124,8 @@ class VecEnv:
         flags = N.SE_FLAG_AUTO_RESET if self.auto_reset else 0
         with torch.cuda.device(self.device):
             N.check(lib.se_create(C.byref(self._h), self.device.index, n, self.env_id_base,
-                                  self.H, self.W, self.water.ctypes.data_as(C.c_void_p), self.P,
-                                  self.port_x.ctypes.data_as(C.c_void_p),
-                                  self.port_y.ctypes.data_as(C.c_void_p),
-                                  self.port_fuel.ctypes.data_as(C.c_void_p),
-                                  self.port_cargo.ctypes.data_as(C.c_void_p), self.seed, flags))
+                                  self.H, self.W, self.water.ctypes.data_as(C.c_void_p), *self._port_args(),
+                                  self.seed, flags))
         # done lists (auto-reset): per-wave segments, double-buffered
         # (include/shipenv.h se_done_layout); records are {env, ep_return bits, ep_len, step}
         seg, nseg = C.c_int64(), C.c_int32()
@@ -171,6 +165,11 @@ class VecEnv:
         d = (t - self.ep_start.to(torch.int64)) & 0xFFFFFFFF
         return torch.where(d >= 2**31, d - 2**32, d).to(torch.int32)
 
+    def _port_args(self):
+        """P and the four port arrays, as se_create and se_set_ports take them."""
+        return (self.P,) + tuple(a.ctypes.data_as(C.c_void_p)
+                                 for a in (self.port_x, self.port_y, self.port_fuel, self.port_cargo))
+
     def _stream(self):
         return C.c_void_p(_raw_stream(self._dev_index))
 
@@ -193,10 +192,7 @@ class VecEnv:
         self.port_fuel = _i32(port_fuel)
         self.port_cargo = _i32(port_cargo)
         self.P = len(self.port_x)
-        N.check(N.lib().se_set_ports(self._h, self.P, self.port_x.ctypes.data_as(C.c_void_p),
-                                     self.port_y.ctypes.data_as(C.c_void_p),
-                                     self.port_fuel.ctypes.data_as(C.c_void_p),
-                                     self.port_cargo.ctypes.data_as(C.c_void_p)))
+        N.check(N.lib().se_set_ports(self._h, *self._port_args()))
 
     def reset(self, mask=None):
         """reset() (environment.py:227-243) of every env, or of those with mask != 0."""
@@ -256,11 +252,8 @@ class VecEnv:
                 raise ValueError(f"mark_after must be in [0, {a.shape[0]}], got {mark_after}")
             rc = N.lib().se_step_seq_mark(self._h, a.data_ptr(), ld, a.shape[0],
                                           _raw_stream(self._dev_index), mark.cuda_event, int(mark_after))
-            if rc:
-                N.check(rc)
-            self._keep = a
-            return self.reward, self.done, self.err
-        rc = self._se_step_seq(self._h, a.data_ptr(), ld, a.shape[0], _raw_stream(self._dev_index))
+        else:
+            rc = self._se_step_seq(self._h, a.data_ptr(), ld, a.shape[0], _raw_stream(self._dev_index))
         if rc:
             N.check(rc)
         self._keep = a

@@ -117,6 +117,33 @@ def test_single_env_every_actor():
         env.close()
 
 
+def test_world_image_past_64_kib():
+    """The 256 x 256, 254-port world of rollout_support.max_world: its cell codes alone are
+    64 KiB, so the image is past the dynamic LDS a launch gets without asking for more and
+    se_mcts_choose has to ask. n = 5 (a wave's first lanes), 3 simulations, short rollouts, from
+    the ships a reset and eight steps of the synthetic agent leave."""
+    import rollout_support as RS
+    from shippingenv_amd.mcts import VecMCTSAgent
+
+    w = RS.max_world()
+    env = w.env(5, seed=MS.SEED)
+    env.reset()
+    for t in range(8):
+        env.step(env.gen_actions(t))
+    st = oracle_state(env)
+    ships = [(int(st.x[i]), int(st.y[i]), float(st.fuel[i]), int(st.cargo[i]), int(st.origin[i]), int(st.dest[i]))
+             for i in range(env.n)]
+    agent = VecMCTSAgent(env, num_simulations=3, max_rollout_steps=4, max_attempts=8)
+    ow = w.oracle(O)
+    want = [MS.decide(O, ow, sh, seed=MS.SEED, id0=i * 3, S=3, c=1.4, max_steps=4, max_attempts=8)
+            for i, sh in enumerate(ships)]
+    assert_decisions(choose(agent, 3, 0), want, "max world")
+    assert any(len(d.nodes) > 1 for d in want)  # trees grew: their steps read the staged image
+    assert_unchanged(env, st, "max world")
+    agent.close()
+    env.close()
+
+
 def test_more_than_64_possible_actions():
     """Fuel 0 on an origin port that stocks 100: TAKE_CARGO 1..100, past the 64 action indices
     the kernel keeps as a bit mask, so the untried action is found by counting. With
