@@ -359,6 +359,93 @@ int se_rollout_plan(se_env* env, const int32_t* src, int64_t m,
                     const int64_t* ids /* NULL: rollout_base + r */, int64_t rollout_base,
                     double* ret, int32_t* counted, int32_t* status, const se_plan_out* out, void* stream);
 
+/* The navigator (an extension: the reference has no such component): route tables for the env's
+ * static world, an expert policy that reads them, and rollouts that play it.
+ *
+ * Tables, built on the host by one breadth-first pass per port from the water mask and the ports
+ * as se_create sees them (ports stamped non-ground, x the row), cell c = x * W + y:
+ *   field[p][c]  u16: the least number of moves from c to port p's cell, every cell of the path
+ *                in the map and not ground; 0 on the port's cell, SE_NAV_INF on ground and where
+ *                there is no such path (no finite value reaches SE_NAV_INF for H, W <= 256).
+ *   dir[p][c]    u8: the move k of the in-map neighbour with the smallest finite field[p] value,
+ *                k = 0..3 = N (0,-1), E (-1,0), S (0,1), W (1,0) on (x, y) as in the agent index;
+ *                the lowest k wins a tie; SE_NAV_NONE when no neighbour is finite (an enclosed
+ *                cell, a 1 x 1 map). On the port's own cell it names a neighbour with field 1:
+ *                step off and come back, since the step tests for an arrival only inside a move.
+ * se_nav_build_host uses no device. Its checks are se_create's (sides 1..256, P 0..254, ports in
+ * the map); P = 0 is a no-op; field and dir hold P * H * W entries each, either may be NULL.
+ *
+ * The policy, on a ship (x, y, fuel, cargo, origin, dest) with cur the port on its cell (the
+ * first one there) or none, the first rule that applies:
+ *   1. dest None: at sea SE_NAV_NO_DEST; on a port SELECT_PORT q, the port q != origin with the
+ *      smallest field[q][c] in 0 < field < SE_NAV_INF, the lowest q on a tie; none: SE_NAV_NO_DEST.
+ *   2. on a port, fuel < refuel_below and its fuel stock >= 1: TAKE_FUEL of the whole stock.
+ *   3. on a port, cargo == 0, load > 0 and its cargo stock >= 1: TAKE_CARGO min(load, stock).
+ *   4. k = dir[dest][c]: SE_NAV_NONE is SE_NAV_UNREACHABLE, else MOVE_SHIP by move k.
+ * A ship outside the map, or with a dest that names no port, is SE_NAV_UNREACHABLE: no table index
+ * is formed from such a value, nor from a dir byte of SE_NAV_NONE. On any status but SE_NAV_OK the
+ * action is (0, 0, 0), which se_step_typed answers with SE_ERR_BAD_CATEGORY and an untouched env.
+ * No emitted action raises in the step: moves go to in-map non-ground cells, takes are within
+ * stock, the selected port is not the origin. refuel_below compares as a double does (NaN never
+ * refuels, +inf always); load < 0 is SE_EINVAL.
+ *
+ * The handle holds the tables for the env's current world on the host and the device. Destroy it
+ * before its env. After se_set_ports every call but se_nav_rebuild and se_nav_destroy answers
+ * SE_ESTATE ("the ports changed since se_nav_create: call se_nav_rebuild") and launches nothing;
+ * se_nav_rebuild synchronises the device and is not capturable. P = 0 is a valid handle: its
+ * calls report every env as SE_NAV_NO_DEST or SE_NAV_UNREACHABLE. max_leg is the largest finite
+ * field value between two ports' cells, 0 if there is none. */
+#define SE_NAV_INF 0xFFFF
+#define SE_NAV_NONE 255
+#define SE_NAV_OK 0
+#define SE_NAV_NO_DEST 1
+#define SE_NAV_UNREACHABLE 2
+int se_nav_build_host(int32_t H, int32_t W, const uint8_t* water, int32_t P,
+                      const int32_t* port_x, const int32_t* port_y,
+                      uint16_t* field /* P*H*W or NULL */, uint8_t* dir /* P*H*W or NULL */);
+typedef struct se_nav se_nav;
+int se_nav_create(se_nav** out, se_env* env);
+int se_nav_rebuild(se_nav* nav);
+int se_nav_tables(const se_nav* nav, const uint16_t** d_field, const uint8_t** d_dir, int32_t* max_leg);
+int se_nav_destroy(se_nav* nav);
+
+/* The policy's action for every env of the handle's env (n entries each, 16-byte aligned; the
+ * env's state is only read, nothing is drawn): type, a, b as se_step_typed takes them, status =
+ * SE_NAV_*; agent (NULL: not wanted) the se_step index of the action, -1 where status != SE_NAV_OK
+ * or the amount has no index (the index decodes to TAKE_CARGO 0..49 and TAKE_FUEL 0..199); dist
+ * (NULL: not wanted) field[dest][cell], -1 for dest None, a dest that names no port, a ship outside
+ * the map or SE_NAV_INF. A negative load or a misaligned array is SE_EINVAL whatever the handle;
+ * n = 0 is a no-op. One launch, no allocation, no synchronisation: capturable. */
+int se_nav_actions(se_nav* nav, double refuel_below, int32_t load,
+                   int32_t* type, int32_t* a, int32_t* b, int32_t* status,
+                   int32_t* agent, int32_t* dist, void* stream);
+
+/* Navigated rollouts: se_rollout_plan's loop with the action of every position computed by the
+ * policy from the rollout's private ship. Rollout r copies env src[r] (the env's state and
+ * counters are only read) and plays positions k = 0 .. steps - 1: a raising step is skipped and
+ * counted in end.raised (by the policy's construction there is none); a counted step adds its f64
+ * reward in order, and one that reports done ends the rollout with SE_PLAN_DONE; a position where
+ * the policy has no action ends it with SE_PLAN_STUCK, stuck_at = k and nav_status the SE_NAV_*
+ * reason, and nothing more is played; running out of positions is SE_PLAN_END. arrivals counts the
+ * steps that arrived at their destination. nav_status is SE_NAV_OK and stuck_at -1 otherwise.
+ * Draws: no new slot. Key (seed, ids ? ids[r] : rollout_base + r); position k reads (k, slot 12)
+ * words 1-3 and (k, slot 13) for a partial loss or an arrival: exactly se_rollout_plan's reads.
+ * A navigated rollout equals se_rollout_plan on the same source and id, fed the action list the
+ * navigator emitted, in ret (bits), counted, raised, done-ness and the end ship.
+ * Misuse (a null required buffer with m > 0, a negative m, steps, rollout_base or load, a
+ * misaligned array) is SE_EINVAL before any launch and whatever the handle; m = 0 is a no-op;
+ * steps = 0 writes ret 0, counted 0 and SE_PLAN_END; a bad src[r] writes SE_PLAN_BAD_SRC with the
+ * zeros and -1 se_rollout_plan writes. One launch, no allocation, no synchronisation: capturable. */
+#define SE_PLAN_STUCK 5   /* the navigator had no action at some position; nav_status says which */
+typedef struct se_nav_out {   /* every pointer may be NULL: not wanted; m entries each */
+    int32_t *arrivals, *nav_status, *stuck_at;
+    se_plan_out end;
+} se_nav_out;
+int se_rollout_nav(se_nav* nav, const int32_t* src, int64_t m, int32_t steps,
+                   double refuel_below, int32_t load,
+                   const int64_t* ids /* NULL: rollout_base + r */, int64_t rollout_base,
+                   double* ret, int32_t* counted, int32_t* status, const se_nav_out* out, void* stream);
+
 /* One MCTS decision per env (agents/mcts.py:240-292, MCTSAgent.choose_action): `simulations`
  * sequential simulations (UCB1 selection with c_param, one expansion, a random rollout of at
  * most max_rollout_steps counted steps, backpropagation) on a private copy of the env, whose

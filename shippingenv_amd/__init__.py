@@ -13,6 +13,8 @@ reset) as gfx950 HIP kernels behind a C-ABI (include/shipenv.h):
   the vectorised DQN training loop;
 * ``shippingenv_amd.mcts.VecMCTSAgent`` (also ``shippingenv_amd.VecMCTSAgent``) — the
   reference's MCTS planner, one decision per env and launch;
+* ``shippingenv_amd.nav.VecNavigator`` (also ``shippingenv_amd.VecNavigator``) — an extension:
+  water-route tables of the static map, an expert policy on them and navigated rollouts;
 * ``shippingenv_amd.maps`` — the map loader (``_initialize_map``);
 * ``shippingenv_amd.dist`` — one process per GPU, env sharding, RCCL stats.
 """
@@ -25,4 +27,8 @@ def __getattr__(name):  # resolved on first use: importing the package stays fre
         from .mcts import VecMCTSAgent
 
         return VecMCTSAgent
+    if name == "VecNavigator":
+        from .nav import VecNavigator
+
+        return VecNavigator
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -31,6 +31,10 @@ SAMPLE_RAISES, SAMPLE_NO_OTHER_PORT = -1, -2
 ROLL_DONE, ROLL_MAX_STEPS, ROLL_RAISED, ROLL_ATTEMPTS, ROLL_BAD_SRC = 0, 1, 2, 3, 4
 # se_rollout_plan statuses
 PLAN_DONE, PLAN_END, PLAN_BAD_SRC = 0, 1, 4
+# the navigator: table sentinels, se_nav_actions statuses, se_rollout_nav's extra status
+NAV_INF, NAV_NONE = 0xFFFF, 255
+NAV_OK, NAV_NO_DEST, NAV_UNREACHABLE = 0, 1, 2
+PLAN_STUCK = 5
 # se_mcts_choose statuses
 MCTS_OK, MCTS_CUT, MCTS_RAISED, MCTS_NEVER_RETURNS = 0, 1, 2, 3
 MCTS_MAX_SIMULATIONS = 256
@@ -66,6 +70,11 @@ class SePlanOut(C.Structure):
         "raised", "first_err", "first_err_at", "x", "y", "fuel", "cargo", "origin", "dest")]
 
 
+class SeNavOut(C.Structure):
+    """se_nav_out: what se_rollout_nav writes beside ret, counted and status (NULL: not wanted)."""
+    _fields_ = [(name, C.c_void_p) for name in ("arrivals", "nav_status", "stuck_at")] + [("end", SePlanOut)]
+
+
 class SeDoneRec(C.Structure):
     _fields_ = [("env", C.c_int32), ("ep_return", C.c_float), ("ep_len", C.c_int32),
                 ("step", C.c_int32)]
@@ -95,6 +104,13 @@ SIGNATURES = {
     "se_sample_actions": [_P, _P, _P, _P, _u32, _P],
     "se_rollout": [_P, _P, _i64, _i32, _i32, _i64, _P, _P, _P, _P],
     "se_rollout_plan": [_P, _P, _i64, _P, _P, _P, _i64, _i32, _P, _P, _i64, _P, _P, _P, C.POINTER(SePlanOut), _P],
+    "se_nav_build_host": [_i32, _i32, _P, _i32, _P, _P, _P, _P],
+    "se_nav_create": [C.POINTER(_P), _P],
+    "se_nav_rebuild": [_P],
+    "se_nav_tables": [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_i32)],
+    "se_nav_destroy": [_P],
+    "se_nav_actions": [_P, C.c_double, _i32, _P, _P, _P, _P, _P, _P, _P],
+    "se_rollout_nav": [_P, _P, _i64, _i32, C.c_double, _i32, _P, _i64, _P, _P, _P, C.POINTER(SeNavOut), _P],
     "se_mcts_create": [C.POINTER(_P), _P, _i32],
     "se_mcts_choose": [_P, _i32, C.c_double, _i32, _i32, _i64, _P, _P, _P, _P, _P, _P, _P],
     "se_mcts_destroy": [_P],

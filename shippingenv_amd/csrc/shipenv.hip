@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "../../include/shipenv.h"
+#include "navfield.h"
 #include "philox.h"
 #include "step_lean.h"
 
@@ -87,6 +88,7 @@ struct se_env {
     uint32_t flags = 0;
     uint64_t step_t = 0, epoch = 0;
     std::vector<uint8_t> water;  // H*W, 0 = ground
+    std::vector<int32_t> port_x, port_y;  // the ports of the uploaded world (se_nav builds its tables from them)
     uint32_t* d_world = nullptr;
     int64_t seg = 0;    // done-list segment stride (records per wave-iteration: 256)
     int64_t iters = 1;  // groups per thread of the step kernel
@@ -265,6 +267,8 @@ int upload_world(se_env* env, int32_t P, const int32_t* px, const int32_t* py, c
     if (rc) return rc;
     HIP_TRY(hipMemcpy(env->d_world, img.data(), (size_t)d.padded() * 4, hipMemcpyHostToDevice));
     env->dims = d;
+    env->port_x.assign(px, px + P);
+    env->port_y.assign(py, py + P);
     env->cmax = env->fmax = env->stock_cargo_max = 0;
     for (int i = 0; i < P; ++i) {  // amounts 1..49 / 1..199 exist (utils/preprocessing.py:93-108)
         env->cmax = std::max(env->cmax, std::min(pc[i], 49));
@@ -932,3 +936,4 @@ int se_host_destroy(se_host* h) {
 #include "replay.h"
 #include "qtrain.h"
 #include "server.h"
+#include "nav.h"
