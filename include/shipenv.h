@@ -487,6 +487,35 @@ int se_mcts_choose(se_mcts* m, int32_t simulations, double c_param, int32_t max_
                    int32_t* status, se_mcts_node* tree, int32_t* tree_count, void* stream);
 int se_mcts_destroy(se_mcts* m);
 
+/* se_mcts_choose with navigator playouts (an extension: the reference's playout is its random
+ * policy): every leaf is valued by playing the navigator of `nav`, with refuel_below and load as
+ * in se_nav_actions, on the simulation's private ship. Outputs, tree layout, ids (mcts_base +
+ * (env_id_base + i) * simulations + s), the tree-step draws and the root fallback draw are
+ * exactly se_mcts_choose's; only the playout differs. Position k = 0 .. max_rollout_steps - 1 of
+ * a playout asks the policy for its action: any status but SE_NAV_OK ends the playout with what it
+ * has summed; otherwise the action is stepped, a raising step is skipped and not counted (by the
+ * policy's construction there is none), a counted step adds its f64 reward in order and one that
+ * reports done ends the playout. There is no attempts budget: the positions bound the loop.
+ * Draws: the playout draws what se_rollout_nav draws for ids[r] = id, (k, slot 12) words 1-3 and
+ * (k, slot 13) for a partial loss or an arrival. No new slot; word 0 of slot 12 is not read.
+ * status: SE_MCTS_OK; SE_MCTS_STUCK where some playout ended without an action (sticky, like
+ * SE_MCTS_CUT); SE_MCTS_RAISED and SE_MCTS_NEVER_RETURNS only from the empty argmax and from the
+ * root fallback (a navigator playout never raises), and they win over SE_MCTS_STUCK; SE_MCTS_CUT
+ * does not occur.
+ * Misuse (a null m or nav, load < 0, a NaN c_param, a negative max_rollout_steps or mcts_base,
+ * simulations outside 1..max_simulations, ids that overflow int64, misaligned or half-given
+ * outputs, a nav made on another env than m's) is SE_EINVAL before any launch and whatever the
+ * handles' state. A nav whose ports changed is SE_ESTATE ("the ports changed since se_nav_create:
+ * call se_nav_rebuild") and launches nothing; n = 0 is a no-op. refuel_below compares as a double
+ * does (NaN never refuels). The env's state and counters are only read. One launch, no
+ * allocation, no synchronisation: capturable. */
+#define SE_MCTS_STUCK 4   /* some playout ended where the navigator had no action; the search
+                             went on with that playout's partial return */
+int se_mcts_choose_nav(se_mcts* m, se_nav* nav, double refuel_below, int32_t load,
+                       int32_t simulations, double c_param, int32_t max_rollout_steps,
+                       int64_t mcts_base, int32_t* type, int32_t* a, int32_t* b, int32_t* status,
+                       se_mcts_node* tree, int32_t* tree_count, void* stream);
+
 /* Batched tabular SARSA (agents/sarsa.py): one learner with one dense f64 Q-table in device
  * memory, the env's n envs stepping it together. One se_sarsa_step runs the body of train's
  * inner loop (:255-272) for every env: a fresh env first takes choose_action(state) as its

@@ -37,6 +37,7 @@ NAV_OK, NAV_NO_DEST, NAV_UNREACHABLE = 0, 1, 2
 PLAN_STUCK = 5
 # se_mcts_choose statuses
 MCTS_OK, MCTS_CUT, MCTS_RAISED, MCTS_NEVER_RETURNS = 0, 1, 2, 3
+MCTS_STUCK = 4  # se_mcts_choose_nav alone
 MCTS_MAX_SIMULATIONS = 256
 # se_sarsa_step statuses
 SARSA_OK, SARSA_CUT, SARSA_RAISED, SARSA_NEVER_RETURNS = 0, 1, 2, 3
@@ -113,6 +114,7 @@ SIGNATURES = {
     "se_rollout_nav": [_P, _P, _i64, _i32, C.c_double, _i32, _P, _i64, _P, _P, _P, C.POINTER(SeNavOut), _P],
     "se_mcts_create": [C.POINTER(_P), _P, _i32],
     "se_mcts_choose": [_P, _i32, C.c_double, _i32, _i32, _i64, _P, _P, _P, _P, _P, _P, _P],
+    "se_mcts_choose_nav": [_P, _P, C.c_double, _i32, _i32, C.c_double, _i32, _i64, _P, _P, _P, _P, _P, _P, _P],
     "se_mcts_destroy": [_P],
     "se_sarsa_create": [C.POINTER(_P), _P, _i64],
     "se_sarsa_layout": [_P, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)],

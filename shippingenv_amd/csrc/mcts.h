@@ -3,17 +3,20 @@
 // the tree in a buffer the handle owns, its kernel, and se_mcts_create / se_mcts_choose /
 // se_mcts_destroy.
 //
-// A fragment of shipenv.hip's translation unit, included at its end after qpolicy.h: not a
-// stand-alone header. Uses world.h (WorldDims, LdsWorld, stage_world, sqrt_rn), env_core.h
-// (Ship, Pending, env_key), rollout.h (sample_action, drawn_step, rollout_run), philox.h, and
-// the host side's se_env, check_ready, fail, HIP_TRY, DeviceGuard, aligned16,
-// device_free and world_lds (host.h).
+// A fragment of shipenv.hip's translation unit, included at its end after qpolicy.h and nav.h:
+// not a stand-alone header. Uses world.h (WorldDims, LdsWorld, stage_world, sqrt_rn), env_core.h
+// (Ship, Pending, env_key), rollout.h (sample_action, drawn_step, rollout_run), nav.h (NavTables,
+// nav_playout, se_nav, nav_ready), philox.h, and the host side's se_env, check_ready, fail,
+// HIP_TRY, DeviceGuard, aligned16, device_free and world_lds (host.h).
 //
 // One lane runs choose_action for one env: S = num_simulations sequential simulations
 // (selection by UCB1, one expansion, a random rollout, backpropagation) on a private Ship
 // copy, then best_child(c_param=0) over the root's children. The env's state is only read.
 // A tree step is drawn_step and the rollout is rollout_run, the code of se_rollout: a step
-// here is the step everywhere.
+// here is the step everywhere. The kernel is a template over the playout: MctsRandomPlayout is
+// the reference's (se_mcts_choose); MctsNavPlayout values a leaf with the navigator instead
+// (se_mcts_choose_nav, an extension), nav.h's nav_playout on the same private Ship. Everything
+// but the playout is one text for both.
 //
 // The reference, restated with its quirks:
 //   * is_terminal() is never true: _build_state has no "done" key (environment.py:202-225),
@@ -43,6 +46,8 @@
 // a partial loss or an arrival, block (d, slot 19): three beta uniforms, the new destination.
 // The rollout draws what se_rollout draws for rollout_base + r = id: (attempt, slots 12, 13).
 // The root fallback (:292) reads word 0 of (0xFFFFFFFF, slot 18) of simulation 0's key.
+// The navigator playout draws what se_rollout_nav draws for ids[r] = id: (position, slot 12)
+// words 1-3 and (position, slot 13); word 0 of slot 12 is not read.
 //
 // Tree storage: SoA [node][env] in a scratch buffer the handle owns, so the lanes of a wave
 // touch neighbouring addresses ("MCTS decisions"): a 16-byte record per node and
@@ -178,7 +183,38 @@ __device__ __forceinline__ int mcts_untried(const MctsArgs& A, int64_t i, int no
     }
 }
 
-__global__ __launch_bounds__(kMctsBlock) void mcts_kernel(MctsArgs A) {
+// The playouts. run() plays from the simulation's ship s under its key, leaves the return in ret
+// and answers as rollout_run does: SE_ROLL_RAISED where the decision raises there (sample_type:
+// the SE_SAMPLE_* type), SE_ROLL_ATTEMPTS where the playout stopped early with a partial return,
+// which marks the decision with the sticky status kPartial.
+struct MctsRandomPlayout {  // _rollout (:211-238): rollout_run, the code of se_rollout
+    using Args = MctsArgs;
+    static constexpr int kPartial = SE_MCTS_CUT;
+    static __device__ __forceinline__ int32_t run(const Args& A, const LdsWorld& w, Ship& s, const Key& key,
+                                                  double& ret, int& sample_type) {
+        int32_t steps;
+        return rollout_run(w, s, key, A.max_steps, A.max_attempts, ret, steps, sample_type);
+    }
+};
+
+struct MctsNavArgs : MctsArgs {  // max_attempts is not read
+    NavTables tab;
+    double refuel_below;
+    int32_t load;
+};
+
+struct MctsNavPlayout {  // the navigator for max_steps positions: never raises, never cut
+    using Args = MctsNavArgs;
+    static constexpr int kPartial = SE_MCTS_STUCK;
+    static __device__ __forceinline__ int32_t run(const Args& A, const LdsWorld& w, Ship& s, const Key& key,
+                                                  double& ret, int&) {
+        return nav_playout(w, A.tab, s, key, A.max_steps, A.refuel_below, A.load, ret) ? SE_ROLL_MAX_STEPS
+                                                                                       : SE_ROLL_ATTEMPTS;
+    }
+};
+
+template <class Playout>
+__global__ __launch_bounds__(kMctsBlock) void mcts_kernel(typename Playout::Args A) {
     extern __shared__ uint32_t lds[];
     const LdsWorld w = stage_world(A.world, A.dims, lds);
     const int S = A.sims;
@@ -233,14 +269,13 @@ __global__ __launch_bounds__(kMctsBlock) void mcts_kernel(MctsArgs A) {
             }
             // simulation (:282): _rollout sits outside any try
             double ret;
-            int32_t steps;
             int sample_type;
-            const int32_t rs = rollout_run(w, s, key, A.max_steps, A.max_attempts, ret, steps, sample_type);
+            const int32_t rs = Playout::run(A, w, s, key, ret, sample_type);
             if (rs == SE_ROLL_RAISED) {
                 raised = sample_type;
                 break;
             }
-            if (rs == SE_ROLL_ATTEMPTS) status = SE_MCTS_CUT;
+            if (rs == SE_ROLL_ATTEMPTS) status = Playout::kPartial;
             // backpropagation (:149-159)
             for (;;) {
                 const int64_t at = (int64_t)node * A.n + i;
@@ -326,13 +361,15 @@ int se_mcts_create(se_mcts** out, se_env* env, int32_t max_simulations) {
     return SE_OK;
 }
 
-int se_mcts_choose(se_mcts* m, int32_t simulations, double c_param, int32_t max_rollout_steps,
-                   int32_t max_attempts, int64_t mcts_base, int32_t* type, int32_t* a, int32_t* b,
-                   int32_t* status, se_mcts_node* tree, int32_t* tree_count, void* stream) {
-    if (!m) return fail(SE_EINVAL, "null mcts handle");
-    se_env* env = m->env;
-    int rc = check_ready(env);
-    if (rc) return rc;
+}  // extern "C"
+
+namespace {
+
+// What both entry points check of their arguments, none of it the env's or a handle's state.
+int mcts_check(const se_mcts* m, int32_t simulations, double c_param, int32_t max_rollout_steps,
+               int32_t max_attempts, int64_t mcts_base, const int32_t* type, const int32_t* a, const int32_t* b,
+               const int32_t* status, const se_mcts_node* tree, const int32_t* tree_count) {
+    const se_env* env = m->env;
     if (env->n != m->n) return fail(SE_EINVAL, "the env's size changed since se_mcts_create");
     if (simulations < 1 || simulations > m->max_sims)
         return fail(SE_EINVAL, "simulations must be in 1..max_simulations");
@@ -349,12 +386,21 @@ int se_mcts_choose(se_mcts* m, int32_t simulations, double c_param, int32_t max_
     if (!aligned16(type) || !aligned16(a) || !aligned16(b) || !aligned16(status) || !aligned16(tree) ||
         !aligned16(tree_count))
         return fail(SE_EINVAL, "outputs must be 16-byte aligned");
+    return SE_OK;
+}
+
+// One launch of the decision kernel with playout Playout; `extra` fills what its Args add.
+template <class Playout, class Extra>
+int mcts_launch(se_mcts* m, int32_t simulations, double c_param, int32_t max_rollout_steps, int32_t max_attempts,
+                int64_t mcts_base, int32_t* type, int32_t* a, int32_t* b, int32_t* status, se_mcts_node* tree,
+                int32_t* tree_count, void* stream, Extra extra) {
+    se_env* env = m->env;
     DeviceGuard g(env->device);
     size_t lds;
-    rc = world_lds<mcts_kernel>(env, lds);
+    const int rc = world_lds<mcts_kernel<Playout>>(env, lds);
     if (rc) return rc;
     const size_t nodes = (size_t)(m->max_sims + 1) * (size_t)m->n;
-    MctsArgs A{};
+    typename Playout::Args A{};
     A.world = env->d_world;
     A.dims = env->dims;
     A.n = env->n;
@@ -375,10 +421,50 @@ int se_mcts_choose(se_mcts* m, int32_t simulations, double c_param, int32_t max_
     A.status = status;
     A.tree = tree;
     A.tree_count = tree_count;
+    extra(A);
     const int64_t blocks = (env->n + kMctsBlock - 1) / kMctsBlock;
-    mcts_kernel<<<(int)std::min<int64_t>(blocks, kMctsMaxBlocks), kMctsBlock, lds, (hipStream_t)stream>>>(A);
+    mcts_kernel<Playout><<<(int)std::min<int64_t>(blocks, kMctsMaxBlocks), kMctsBlock, lds, (hipStream_t)stream>>>(A);
     HIP_TRY(hipGetLastError());
     return SE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int se_mcts_choose(se_mcts* m, int32_t simulations, double c_param, int32_t max_rollout_steps,
+                   int32_t max_attempts, int64_t mcts_base, int32_t* type, int32_t* a, int32_t* b,
+                   int32_t* status, se_mcts_node* tree, int32_t* tree_count, void* stream) {
+    if (!m) return fail(SE_EINVAL, "null mcts handle");
+    int rc = check_ready(m->env);
+    if (rc) return rc;
+    rc = mcts_check(m, simulations, c_param, max_rollout_steps, max_attempts, mcts_base, type, a, b, status, tree,
+                    tree_count);
+    if (rc || m->env->n == 0) return rc;
+    return mcts_launch<MctsRandomPlayout>(m, simulations, c_param, max_rollout_steps, max_attempts, mcts_base, type,
+                                          a, b, status, tree, tree_count, stream, [](MctsArgs&) {});
+}
+
+int se_mcts_choose_nav(se_mcts* m, se_nav* nav, double refuel_below, int32_t load, int32_t simulations,
+                       double c_param, int32_t max_rollout_steps, int64_t mcts_base, int32_t* type, int32_t* a,
+                       int32_t* b, int32_t* status, se_mcts_node* tree, int32_t* tree_count, void* stream) {
+    // the arguments first: misuse is reported whatever the handles' state
+    if (!m) return fail(SE_EINVAL, "null mcts handle");
+    if (!nav) return fail(SE_EINVAL, "null nav handle");
+    if (load < 0) return fail(SE_EINVAL, "load must be >= 0");
+    int rc = mcts_check(m, simulations, c_param, max_rollout_steps, 0, mcts_base, type, a, b, status, tree,
+                        tree_count);
+    if (rc) return rc;
+    if (nav->env != m->env) return fail(SE_EINVAL, "the nav handle was made on another env");
+    rc = nav_ready(nav);
+    if (rc || m->env->n == 0) return rc;
+    const NavTables tab{nav->d_field, nav->d_dir};
+    return mcts_launch<MctsNavPlayout>(m, simulations, c_param, max_rollout_steps, 0, mcts_base, type, a, b, status,
+                                       tree, tree_count, stream, [&](MctsNavArgs& A) {
+                                           A.tab = tab;
+                                           A.refuel_below = refuel_below;
+                                           A.load = load;
+                                       });
 }
 
 int se_mcts_destroy(se_mcts* m) {

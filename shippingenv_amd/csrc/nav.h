@@ -2,9 +2,11 @@
 // nav.h — the navigator (an extension: the reference has no such component): the expert policy
 // nav_action on the route tables of navfield.h, the two kernels that run it (se_nav_actions on
 // the env's state, se_rollout_nav on private copies), and the se_nav handle that builds the
-// tables on the host and keeps them on the device.
+// tables on the host and keeps them on the device; and nav_playout, the rollout's loop for one
+// lane, which the MCTS decision kernel plays as its playout.
 //
-// A fragment of shipenv.hip's translation unit, included at its end: not a stand-alone header.
+// A fragment of shipenv.hip's translation unit, included at its end before mcts.h (whose
+// se_mcts_choose_nav plays nav_playout below): not a stand-alone header.
 // Uses world.h (WorldDims, LdsWorld, world_view, stage_world), env_core.h (Ship, Pending,
 // env_key), rollout.h (drawn_step), philox.h, navfield.h, and the host side's se_env, check_ready,
 // fail, HIP_TRY, DeviceGuard, device_reserve, device_free, world_lds, aligned16 (host.h) and
@@ -84,6 +86,27 @@ __device__ __forceinline__ int32_t nav_agent_index(int P, const NavAction& act) 
     if (act.ty == 2) return 4 + act.a;
     if (act.ty == 4) return act.a <= 49 ? 4 + P + act.a : -1;
     return act.a <= 199 ? 54 + P + act.a : -1;
+}
+
+// se_rollout_nav's loop for one lane, position for position and draw for draw: the navigator
+// played on the private ship s for at most `steps` positions under `key`, the counted steps'
+// rewards summed in order into total. A raising step is skipped and not counted (by the policy's
+// construction there is none); a counted step that reports done ends it. False where the
+// navigator had no action at some position ("stuck"): total is what was summed until then.
+// The playout of se_mcts_choose_nav (mcts.h); nav_rollout_kernel keeps its wave-ballot loop.
+__device__ __forceinline__ bool nav_playout(const LdsWorld& w, const NavTables& t, Ship& s, const Key& key,
+                                            int32_t steps, double refuel_below, int32_t load, double& total) {
+    total = 0.0;
+    for (int32_t k = 0; k < steps; ++k) {
+        const NavAction act = nav_action(w, t, s, refuel_below, load);
+        if (act.status != SE_NAV_OK) return false;
+        const U4 d = draw(key, (uint32_t)k, kSlotRollout);
+        const Pending p = drawn_step(w, s, key, (uint32_t)k, kSlotRolloutB, d, act.ty, act.a, act.b);
+        if (p.e != SE_ERR_OK) continue;
+        total += p.r;
+        if (p.dead) break;
+    }
+    return true;
 }
 
 struct NavActionsArgs {

@@ -931,9 +931,9 @@ int se_host_destroy(se_host* h) {
 
 // the fused DQN policy step (same translation unit: world image, env handle, Philox)
 #include "qpolicy.h"
+#include "nav.h"   // before mcts.h: se_mcts_choose_nav plays the navigator
 #include "mcts.h"
 #include "sarsa.h"
 #include "replay.h"
 #include "qtrain.h"
 #include "server.h"
-#include "nav.h"

@@ -3,6 +3,8 @@
 One se_mcts_choose launch runs choose_action (:240-292) for every env: num_simulations
 sequential simulations per env on a private copy of its state (UCB1 selection, one expansion,
 a random rollout, backpropagation), then best_child(c_param=0). The env's state is only read.
+With a VecNavigator the rollout is the navigator's instead of the random policy's
+(se_mcts_choose_nav, an extension: the tree stays the reference's).
 Nothing here falls back to the host: a missing kernel is an error.
 """
 from __future__ import annotations
@@ -15,8 +17,9 @@ import torch
 from . import _native as N
 from ._native import _ptr
 
-# se_mcts_choose statuses (include/shipenv.h SE_MCTS_*)
+# se_mcts_choose statuses (include/shipenv.h SE_MCTS_*); STUCK from se_mcts_choose_nav alone
 OK, CUT, RAISED, NEVER_RETURNS = N.MCTS_OK, N.MCTS_CUT, N.MCTS_RAISED, N.MCTS_NEVER_RETURNS
+STUCK = N.MCTS_STUCK
 
 # Every node of every env's search tree, [n, simulations + 1] device tensors in creation order
 # (node 0 the root: parent -1, no action); count [n] = nodes written per env.
@@ -32,11 +35,22 @@ class VecMCTSAgent:
     Simulation s of env i of call k draws from Philox(seed, id) with
     id = mcts_base + (env_id_base + i) * num_simulations + s; mcts_base advances by
     stride * num_simulations per call. stride defaults to env.n: in a sharded run set it to
-    the global number of envs, so that the ids of all shards and calls stay disjoint."""
+    the global number of envs, so that the ids of all shards and calls stay disjoint.
+
+    navigator: a VecNavigator of the same env. Every playout is then the navigator's policy
+    (its refuel_below, the derived default included, and its load) for max_rollout_steps
+    positions on the simulation's ship, drawn as VecNavigator.rollout draws for the simulation's
+    id; max_attempts is ignored in that mode (there is nothing to retry), CUT does not occur, and
+    a decision one of whose playouts ended where the navigator had no action has status STUCK.
+    A navigator whose tables were made for other ports (env.set_ports) is rebuilt first, as in
+    its own calls. With navigator=None nothing changes."""
 
     def __init__(self, env, num_simulations=50, exploration_param=1.4, max_rollout_steps=100,
-                 max_attempts=None):
+                 max_attempts=None, navigator=None):
+        if navigator is not None and navigator.env is not env:
+            raise ValueError("the navigator was made on another env")
         self.env = env
+        self.navigator = navigator
         self.num_simulations = int(num_simulations)
         self.exploration_param = float(exploration_param)
         self.max_rollout_steps = int(max_rollout_steps)
@@ -52,16 +66,22 @@ class VecMCTSAgent:
     def choose_action(self, return_tree=False):
         """-> (type, a, b, status) int32 device tensors, the typed actions of step_typed;
         with return_tree=True also an MCTSTree. The four tensors are reused by the next call.
-        Where status is RAISED or NEVER_RETURNS the type is the negative SAMPLE_* code."""
+        Where status is RAISED or NEVER_RETURNS the type is the negative SAMPLE_* code.
+        Status STUCK (navigator playouts alone) still comes with the chosen action."""
         env, S = self.env, self.num_simulations
         ty, a, b, status = self._out
         raw = cnt = None
         if return_tree:
             raw = torch.zeros((env.n, S + 1, 8), dtype=torch.int32, device=env.device)  # se_mcts_node
             cnt = torch.zeros(env.n, dtype=torch.int32, device=env.device)
-        N.check(N.lib().se_mcts_choose(self._h, S, self.exploration_param, self.max_rollout_steps,
-                                       self.max_attempts, self.mcts_base, _ptr(ty), _ptr(a), _ptr(b),
-                                       _ptr(status), _ptr(raw), _ptr(cnt), env._stream()))
+        tail = (self.mcts_base, _ptr(ty), _ptr(a), _ptr(b), _ptr(status), _ptr(raw), _ptr(cnt), env._stream())
+        nav = self.navigator
+        if nav is None:
+            N.check(N.lib().se_mcts_choose(self._h, S, self.exploration_param, self.max_rollout_steps,
+                                           self.max_attempts, *tail))
+        else:  # through the navigator's call: a stale handle is rebuilt and asked once more
+            nav._call(lambda h, *args: N.lib().se_mcts_choose_nav(self._h, h, *args), nav.refuel_below,
+                      nav.load, S, self.exploration_param, self.max_rollout_steps, *tail)
         self.mcts_base += self.stride * S
         self.calls += 1
         if not return_tree:

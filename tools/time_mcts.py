@@ -5,7 +5,11 @@ se_rollout batch of n rollouts from the same states, S of which are nearly all o
 env steps; ratio = decision / (S x rollout batch) is the tree's overhead. Both are timed with
 events, alternating, `--runs` times. One JSON line per n.
 
-    python tools/time_mcts.py [--log2n 12 18] [--runs 3] [--sims 50] [--steps 100]
+    python tools/time_mcts.py [--log2n 12 18] [--runs 3] [--sims 50] [--steps 100] [--playout random|nav|both]
+
+--playout nav times se_mcts_choose_nav instead (VecMCTSAgent with a VecNavigator of --load and the
+derived refuel_below; its yardstick is one se_rollout_nav batch); both times the two decisions
+of one build in alternating rounds from the same states (nav_* fields beside the random ones).
 
 --cpu-reference DIR times the reference's own MCTSAgent.choose_action (DIR: a checkout of the
 reference, for agents/ and utils/) on the N = 1 drop-in host stepper instead: a CPU number, for
@@ -59,6 +63,8 @@ def main():
     p.add_argument("--sims", type=int, default=50)
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--seed", type=int, default=2026)
+    p.add_argument("--playout", choices=("random", "nav", "both"), default="random")
+    p.add_argument("--load", type=int, default=0, help="--playout nav / both: the navigator's load")
     p.add_argument("--cpu-reference", metavar="DIR")
     p.add_argument("--decisions", type=int, default=10, help="--cpu-reference: decisions timed")
     a = p.parse_args()
@@ -67,6 +73,7 @@ def main():
     import torch
 
     from shippingenv_amd.mcts import VecMCTSAgent
+    from shippingenv_amd.nav import VecNavigator
     from shippingenv_amd.vec import VecEnv
 
     def timed(fn):
@@ -83,26 +90,42 @@ def main():
         env.reset()
         for t in range(50):
             env.step(env.gen_actions(t))
-        agent = VecMCTSAgent(env, num_simulations=a.sims, max_rollout_steps=a.steps)
         src = torch.arange(n, dtype=torch.int32, device=env.device)
-        agent.choose_action()  # warm
-        env.rollout(src, max_steps=a.steps, rollout_base=0)
+        row = {"n": n, "sims": a.sims, "steps": a.steps}
+        legs = []  # (field prefix, agent, one batch of n rollouts of its playout policy -> counted steps)
+        nav = None
+        if a.playout in ("random", "both"):
+            agent = VecMCTSAgent(env, num_simulations=a.sims, max_rollout_steps=a.steps)
+            legs.append(("", agent, lambda base: env.rollout(src, max_steps=a.steps, rollout_base=base)[1]))
+        if a.playout in ("nav", "both"):
+            nav = VecNavigator(env, load=a.load)
+            agent = VecMCTSAgent(env, num_simulations=a.sims, max_rollout_steps=a.steps, navigator=nav)
+            legs.append(("nav_", agent, lambda base: nav.rollout(src, steps=a.steps, rollout_base=base).steps))
+            row.update(load=a.load, refuel_below=nav.refuel_below)
+        for _, agent, rollouts in legs:  # warm
+            agent.choose_action()
+            rollouts(0)
         torch.cuda.synchronize()
-        dec, roll, counted = [], [], []
+        dec, roll, counted = ({pre: [] for pre, _, _ in legs} for _ in range(3))
         for r in range(a.runs):
-            dec.append(timed(agent.choose_action))
-            kept = []
-            roll.append(timed(lambda: kept.append(env.rollout(src, max_steps=a.steps, rollout_base=(r + 1) * n))))
-            counted.append(float(kept[0][1].sum().item()) / n)
-        status = torch.bincount(agent.choose_action()[3], minlength=4).tolist()
-        d, b = sorted(dec)[len(dec) // 2], sorted(roll)[len(roll) // 2]
-        print(json.dumps({"n": n, "sims": a.sims, "steps": a.steps, "decision_ms": [round(v, 4) for v in dec],
-                          "rollout_batch_ms": [round(v, 4) for v in roll],
-                          "counted_steps_per_rollout": round(sum(counted) / len(counted), 2),
-                          "decisions_per_s": round(n / (d * 1e-3), 1),
-                          "ratio_decision_over_sims_x_rollout_batch": round(d / (a.sims * b), 3),
-                          "status_counts": status}), flush=True)
-        agent.close()
+            for pre, agent, rollouts in legs:
+                dec[pre].append(timed(agent.choose_action))
+                kept = []
+                roll[pre].append(timed(lambda: kept.append(rollouts((r + 1) * n))))
+                counted[pre].append(float(kept[0].sum().item()) / n)
+        for pre, agent, _ in legs:
+            status = torch.bincount(agent.choose_action()[3], minlength=5 if pre else 4).tolist()
+            d, b = sorted(dec[pre])[a.runs // 2], sorted(roll[pre])[a.runs // 2]
+            row.update({pre + "decision_ms": [round(v, 4) for v in dec[pre]],
+                        pre + "rollout_batch_ms": [round(v, 4) for v in roll[pre]],
+                        pre + "counted_steps_per_rollout": round(sum(counted[pre]) / a.runs, 2),
+                        pre + "decisions_per_s": round(n / (d * 1e-3), 1),
+                        pre + "ratio_decision_over_sims_x_rollout_batch": round(d / (a.sims * b), 3),
+                        pre + "status_counts": status})
+            agent.close()
+        if nav is not None:
+            nav.close()
+        print(json.dumps(row), flush=True)
         env.close()
 
 
