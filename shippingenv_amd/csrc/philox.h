@@ -260,6 +260,88 @@ __host__ __device__ __forceinline__ U4 draw_gate_pooled(uint32_t k0, uint32_t k1
     return draw_half(k0, k1, g.e1, g.c3, g.hi, g.lo, t);
 }
 
+// The key schedule of one launch: the key words of rounds 1-10, k0 + r W0 and k1 + r W1 at
+// index r. The seed is the same for every env of a launch, so the fused sequence's state-only
+// steps fill it once before the group loop and keep it in vector registers (pin_schedule: as
+// scalars the schedule spilled, which is why philox10 and draw_half recompute it per block).
+// A draw that reads it has no key add at all, and a v_bitop3_b32 of three VGPRs needs no copy.
+struct KeySched {
+    uint32_t k0[10], k1[10];
+};
+// opaque vector registers: the compiler neither folds the words back into scalar adds nor
+// rematerialises them inside the step loop
+__device__ __forceinline__ void pin_schedule(KeySched& s) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) asm volatile("" : "+v"(s.k0[r]), "+v"(s.k1[r]));
+}
+
+__host__ __device__ __forceinline__ KeySched key_schedule(uint32_t k0, uint32_t k1) {
+    KeySched s;
+    for (int r = 0; r < 10; ++r) {
+        s.k0[r] = k0 + (uint32_t)r * kPhiloxW0;
+        s.k1[r] = k1 + (uint32_t)r * kPhiloxW1;
+    }
+    return s;
+}
+
+// draw(k, t, slot) with the key words read from the schedule of (k.k0, k.k1): philox10's rounds
+// without its key adds. For the state-only step's rare whole-block draws (LOSS_r, ARRIVE).
+__host__ __device__ __forceinline__ U4 draw_sched(const KeySched& s, const Key& k, uint32_t t, uint32_t slot) {
+    uint32_t c0 = k.e0, c1 = k.e1, c2 = t, c3 = slot;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)kPhiloxM0 * c0;
+        const uint64_t p1 = (uint64_t)kPhiloxM1 * c2;
+        const uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, s.k0[r]);
+        const uint32_t n2 = xor3((uint32_t)(p0 >> 32), c3, s.k1[r]);
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+    }
+    return U4{{c0, c1, c2, c3}};
+}
+
+// draw_half with the key words read from the schedule: the same rounds, no key add.
+__host__ __device__ __forceinline__ U4 draw_half_sched(const KeySched& s, uint32_t e1, uint32_t vc3, uint32_t hi,
+                                                       uint32_t lo, uint32_t t) {
+    // rounds 1-3, the common parts (as in draw2)
+    const uint64_t q1 = (uint64_t)kPhiloxM1 * t;
+    const uint32_t n0 = xor3((uint32_t)(q1 >> 32), e1, s.k0[0]);
+    const uint64_t q0 = (uint64_t)kPhiloxM0 * n0;
+    const uint32_t n2 = xor3((uint32_t)(q0 >> 32), vc3, s.k1[1]);
+    const uint32_t c3 = (uint32_t)q0;
+    const uint64_t q2 = (uint64_t)kPhiloxM1 * n2;
+    uint32_t a0 = xor3(hi, (uint32_t)q1, s.k0[1]);  // round 2's n0
+    uint32_t a1, a2, a3;
+    {   // round 3
+        const uint64_t p0 = (uint64_t)kPhiloxM0 * a0;
+        a0 = xor3((uint32_t)(q2 >> 32), lo, s.k0[2]);
+        a2 = xor3((uint32_t)(p0 >> 32), c3, s.k1[2]);
+        a1 = (uint32_t)q2;
+        a3 = (uint32_t)p0;
+    }
+#pragma unroll
+    for (int r = 3; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)kPhiloxM0 * a0;
+        const uint64_t p1 = (uint64_t)kPhiloxM1 * a2;
+        a0 = xor3((uint32_t)(p1 >> 32), a1, s.k0[r]);
+        a2 = xor3((uint32_t)(p0 >> 32), a3, s.k1[r]);
+        a1 = (uint32_t)p1;
+        a3 = (uint32_t)p0;
+    }
+    return U4{{a0, a1, a2, a3}};
+}
+
+__host__ __device__ __forceinline__ U4 draw_fuel_sched(const KeySched& s, const Key& k, const PairInv& v, uint32_t t) {
+    return draw_half_sched(s, k.e1, v.c3, v.hi[0], v.lo[0], t);
+}
+
+// the GATE block of the quad whose seed is g, at counter t, under the schedule's key
+__host__ __device__ __forceinline__ U4 draw_gate_pooled_sched(const KeySched& s, const GateSeed& g, uint32_t t) {
+    return draw_half_sched(s, g.e1, g.c3, g.hi, g.lo, t);
+}
+
 // integer uniform on [0, m): high word of r * m (bias < m / 2^32)
 __device__ __forceinline__ int32_t uniform_int(uint32_t r, uint32_t m) {
     return (int32_t)__umulhi(r, m);

@@ -20,7 +20,9 @@
 // step touches f, c and a only). The cell code under the ship is carried too (after a move
 // it is the byte the ground test read at the cell moved to), so a step makes one cell lookup per
 // env, with the table's LDS address riding in the dot product (lds_cell). The action is decoded
-// by two unsigned range compares and the fuel update is one FMA (step_lean.h); each env's gate
+// by two unsigned range compares on act - 4 (the move's against a bound computed once per launch),
+// the fuel scale is one FMA and one add and the fuel update one FMA (step_lean.h); the four cell
+// lookups of a step are issued together and waited for once; each env's gate
 // threshold is carried and looked up again only where its cargo changes. The caller draws FUEL
 // and GATE together (fb, gb: philox.h, draw2), or takes gb from its wave's GATE pool and lets
 // `late` draw FUEL (below). The ranked LOSS draw is step_group_agent's, line
@@ -43,6 +45,20 @@ struct Carried {
 __device__ __forceinline__ uint32_t gate_thr_of(const LdsWorld& w, int cargo) {
     return w.gate_thr[min(max(cargo, 0), 50)];
 }
+// The launch's invariants of the state-only steps: the Philox key schedule in vector registers
+// (philox.h; the pooled loop's FUEL draw, a pool refill and the rare LOSS_r / ARRIVE draws read
+// it, so they compute no key add) and the move test's bound (step_lean.h), a scalar.
+// kSched = false (the kernel without the pool, whose draw2 keeps its scalar keys and which has no
+// 20 registers to spare under 128): no schedule, the rare draws are draw()'s.
+template <bool kSched>
+struct SeqInv {
+    KeySched ks;
+    uint32_t move_bound;
+    __device__ __forceinline__ U4 block(const Key& qk, uint32_t t, uint32_t slot) const {
+        if constexpr (kSched) return draw_sched(ks, qk, t, slot);
+        else return draw(qk, t, slot);
+    }
+};
 // `late` runs after the take block and may set fb: the pooled kernel draws FUEL there and pins
 // the words, which keeps the draw out of the step's last block and, as it happens, cargo and fuel
 // in their registers across the take block (drawn before the call the loop had 10 VALU more, 7
@@ -50,9 +66,9 @@ __device__ __forceinline__ uint32_t gate_thr_of(const LdsWorld& w, int cargo) {
 struct NoLateDraw {
     __device__ __forceinline__ void operator()(U4&) const {}
 };
-template <bool kNt, typename Late = NoLateDraw>
-__device__ __forceinline__ bool step_group_state(const LdsWorld& w, const Key& qk, uint32_t t, U4 fb, const U4& gb,
-                                                 Group<false, false, kNt>& G, Carried& U, Late late = Late{}) {
+template <bool kNt, bool kSched, typename Late = NoLateDraw>
+__device__ __forceinline__ bool step_group_state(const LdsWorld& w, const SeqInv<kSched>& I, const Key& qk, uint32_t t, U4 fb,
+                                                 const U4& gb, Group<false, false, kNt>& G, Carried& U, Late late = Late{}) {
     const int P = w.P;
     const uint32_t lim = (uint32_t)(w.H - 1) | ((uint32_t)(w.W - 1) << 16);
     const uint32_t wh = (uint32_t)w.W | (1u << 16);
@@ -87,37 +103,43 @@ __device__ __forceinline__ bool step_group_state(const LdsWorld& w, const Key& q
         }
     }
     late(fb);
-    uint32_t pos[4];
+    uint32_t pos[4], cp[4], code_cp[4];
     int dst[4], cg[4];
-    bool do_move[4], moved[4];
+    bool do_move[4], moved[4], inb[4], nodest[4];
+    // MOVE (_move_ship :273-339): the four cell lookups first, so their LDS reads are in flight
+    // together and a wave waits for one latency, not four
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t dxy = w.moves[G.a[j] & 3];
+        const uint32_t p = U.pos[j];
+        dst[j] = U.dst[j];
+        const uint32_t np = pk_add_u16(p, dxy);
+        inb[j] = pk_min_u16(np, lim) == np;  // _is_within_map (:284); -1 wraps to 0xffff
+        nodest[j] = dst[j] == SE_NONE;       // :276
+        cp[j] = (!nodest[j] & inb[j]) ? np : p;  // in-range cell for the lookup
+        code_cp[j] = lds_cell(lds_address(w.cell), cp[j], wh);
+    }
+    // carried as full registers (as bytes they are masked again before every select); pinned in
+    // one statement, which is the one wait for the four reads
+    asm("" : "+v"(code_cp[0]), "+v"(code_cp[1]), "+v"(code_cp[2]), "+v"(code_cp[3]));
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         // [0,4) moves (-4..-1 wrap), [4, 4+P) SELECT; the takes are done
         const int act = G.a[j];
-        const int val = (int)((uint32_t)act - 4u);  // only a select reads it
-        const uint32_t dxy = w.moves[act & 3];
+        const int val = (int)((uint32_t)act - 4u);  // the move test and a select read it
         const uint32_t p = U.pos[j];
-        dst[j] = U.dst[j];
         cg[j] = G.c[j];
-        // MOVE (_move_ship :273-339)
-        const uint32_t np = pk_add_u16(p, dxy);
-        const bool inb = pk_min_u16(np, lim) == np;  // _is_within_map (:284); -1 wraps to 0xffff
-        const bool nodest = dst[j] == SE_NONE;       // :276
-        const uint32_t cp = (!nodest & inb) ? np : p;  // in-range cell for the lookup
-        uint32_t code_cp = lds_cell(lds_address(w.cell), cp, wh);
-        // carried as a full register (as a byte it is masked again before every select)
-        asm("" : "+v"(code_cp));
-        const bool ground = code_cp == kCellGround;  // :293
+        const bool ground = code_cp[j] == kCellGround;  // :293
         // step_group_agent's error cascade as the two bits the next state needs (step_lean.h):
         // a move that passed its checks, a SELECT that passed its own (mask arithmetic, no
         // ?: : a branch here would take the LDS lookups with it). A take is not among them: the
         // take guard has applied it, and nothing below reads whether a take passed.
         const bool same = U.org[j] == val;
-        do_move[j] = lean_do_move(act, P, nodest, inb);
+        do_move[j] = lean_do_move_val(val, I.move_bound, nodest[j], inb[j]);
         moved[j] = do_move[j] & !ground;
         const bool sel_ok = lean_sel_ok(act, P, same);
-        pos[j] = moved[j] ? cp : p;
-        U.code[j] = moved[j] ? code_cp : U.code[j];  // the ground test's read
+        pos[j] = moved[j] ? cp[j] : p;
+        U.code[j] = moved[j] ? code_cp[j] : U.code[j];  // the ground test's read
         dst[j] = sel_ok ? val : dst[j];
     }
     uint32_t fire = 0, arrive = 0;
@@ -139,8 +161,7 @@ __device__ __forceinline__ bool step_group_state(const LdsWorld& w, const Key& q
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         // fuel cost (:103-104); a ship that does not move adds -0.0, which leaves every value as it is
-        const double scale = 1.0 + (-0.1 + (double)fb.v[j] * kFifthPerWord);
-        f[j] = lean_fuel(G.f[j], scale, moved[j]);
+        f[j] = lean_fuel(G.f[j], lean_fuel_scale(fb.v[j], kFifthPerWord), moved[j]);
         // the gate (:318-323), as step_group_agent tests it, against the carried threshold
         const bool fires = do_move[j] & (cg[j] > 0) & (gb.v[j] <= U.thr[j]);
         fire |= (uint32_t)fires << j;
@@ -159,7 +180,7 @@ __device__ __forceinline__ bool step_group_state(const LdsWorld& w, const Key& q
     if (fire) {
         uint32_t lt[4], v1[4], v2[4], v3[4];
         const uint32_t rk[4] = {0u, fire & 1u, (uint32_t)__popc(fire & 3u), (uint32_t)__popc(fire & 7u)};
-        U4 rr = draw(qk, t, loss_slot(0));
+        U4 rr = I.block(qk, t, loss_slot(0));
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             lt[j] = rr.v[0];
@@ -170,7 +191,7 @@ __device__ __forceinline__ bool step_group_state(const LdsWorld& w, const Key& q
 #pragma unroll
         for (uint32_t q = 1; q < 4; ++q) {
             if (__popc(fire) > q) {
-                rr = draw(qk, t, loss_slot(q));
+                rr = I.block(qk, t, loss_slot(q));
 #pragma unroll
                 for (int j = (int)q; j < 4; ++j) {
                     const bool take = rk[j] >= q;
@@ -181,8 +202,11 @@ __device__ __forceinline__ bool step_group_state(const LdsWorld& w, const Key& q
                 }
             }
         }
+        // the tail of env j only in a wave where env j of some lane fired: mostly one of the four
+        // (a lane whose env j did not fire keeps its cargo, and with it the carried threshold)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
+            if (__builtin_amdgcn_ballot_w64((fire >> j) & 1u) == 0) continue;
             // beta = the median of the three words * 2^-32 (the conversion is monotone)
             const uint32_t lo = min(v1[j], v2[j]), hi = max(v1[j], v2[j]);
             const uint32_t med = max(lo, min(hi, v3[j]));  // v_med3_u32
@@ -195,7 +219,7 @@ __device__ __forceinline__ bool step_group_state(const LdsWorld& w, const Key& q
         }
     }
     if (arrive) {
-        const U4 ab = draw(qk, t, kSlotArrive);
+        const U4 ab = I.block(qk, t, kSlotArrive);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const bool aj = (arrive >> j) & 1u;
@@ -313,6 +337,18 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
         __syncthreads();
     }
 
+    // what the state-only steps read and no step changes: filled once per launch
+    SeqInv<kPool> I;
+    if (steps > 1) {
+        if constexpr (kPool) {
+            const Key sk = env_key(A.seed, 0);
+            I.ks = key_schedule(sk.k0, sk.k1);
+            pin_schedule(I.ks);
+        }
+        I.move_bound = lean_move_bound(w.P);
+        asm volatile("" : "+s"(I.move_bound));
+    }
+
     BlockStats bs;
     Finished F;
     for (int64_t i = 0; i < A.iters; ++i) {
@@ -352,7 +388,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                     int32_t nxt[4];
                     ld4_full<kNt>(row, g0, nxt);
                     const U4x2 fg = draw2(qk, inv, t);
-                    step_group_state(w, qk, t, fg.fuel, fg.gate, G, U);
+                    step_group_state(w, I, qk, t, fg.fuel, fg.gate, G, U);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
                 }
@@ -384,7 +420,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                             }
                             drew = m != 0;
                             // the window: the largest power of two W <= 8 with m W <= 64
-                            const uint32_t logw = m <= 8 ? 3u : m <= 16 ? 2u : 1u;
+                            const uint32_t logw = gate_window_log2(m);
                             const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
                             wmask = (1u << logw) - 1u;
                             if (m != 0) {
@@ -395,7 +431,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                                 // lane L draws carrier L >> logw's block at window offset L & (W - 1);
                                 // past the last carrier: the last one's again, which nobody's gate reads
                                 const uint4 sd = seeds[min(L >> logw, m - 1u)];
-                                const U4 gw = draw_gate_pooled(qk.k0, qk.k1, GateSeed{sd.x, sd.y, sd.z, sd.w}, t + (L & wmask));
+                                const U4 gw = draw_gate_pooled_sched(I.ks, GateSeed{sd.x, sd.y, sd.z, sd.w}, t + (L & wmask));
                                 pool[L] = make_uint4(gw.v[0], gw.v[1], gw.v[2], gw.v[3]);
                                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                                 __builtin_amdgcn_wave_barrier();
@@ -415,10 +451,10 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                         const uint4 g4 = mine[s & wmask];
                         // FUEL alone, drawn after the take block (step_group_state's `late`)
                         const auto fuel = [&](U4& fb) {
-                            fb = draw_fuel(qk, inv, t);
+                            fb = draw_fuel_sched(I.ks, qk, inv, t);
                             asm volatile("" : "+v"(fb.v[0]), "+v"(fb.v[1]), "+v"(fb.v[2]), "+v"(fb.v[3]));
                         };
-                        const bool took = step_group_state(w, qk, t, U4{}, U4{{g4.x, g4.y, g4.z, g4.w}}, G, U, fuel);
+                        const bool took = step_group_state(w, I, qk, t, U4{}, U4{{g4.x, g4.y, g4.z, g4.w}}, G, U, fuel);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
                         ++s;
@@ -437,7 +473,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                         int32_t nxt[4];
                         ld4_full<kNt>(row, g0, nxt, lane);
                         const U4x2 fg = draw2(qk, inv, t);
-                        step_group_state(w, qk, t, fg.fuel, fg.gate, G, U);
+                        step_group_state(w, I, qk, t, fg.fuel, fg.gate, G, U);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
                     }
