@@ -1,7 +1,7 @@
 #pragma once
 // env_core.h — one step of one env, compiled for the device and for the host
-// (se_host_step_replay, the server wave): Ship, env_key, needs_gate, Pending,
-// env_begin / env_finish, replay_env, beta_part, decode_agent, reset_ship.
+// (se_host_step_replay, the server wave): Ship, load_ship / store_ship, EnvArgs, env_key,
+// needs_gate, Pending, env_begin / env_finish, replay_env, beta_part, decode_agent, reset_ship.
 //
 // A fragment of shipenv.hip's translation unit, included inside its anonymous
 // namespace where this text stood: not a stand-alone header.
@@ -12,6 +12,31 @@ struct Ship {
     int x, y;
     double fuel;
     int cargo, origin, dest;  // origin/dest: SE_NONE = None
+};
+
+// Env i's ship out of the bound state, and back into it (the six fields, nothing else).
+__host__ __device__ __forceinline__ Ship load_ship(const se_state& st, int64_t i) {
+    return Ship{st.x[i], st.y[i], st.fuel[i], st.cargo[i], st.origin[i], st.dest[i]};
+}
+
+__host__ __device__ __forceinline__ void store_ship(const se_state& st, int64_t i, const Ship& s) {
+    st.x[i] = (uint8_t)s.x;
+    st.y[i] = (uint8_t)s.y;
+    st.fuel[i] = s.fuel;
+    st.cargo[i] = s.cargo;
+    st.origin[i] = (uint8_t)s.origin;
+    st.dest[i] = (uint8_t)s.dest;
+}
+
+// What the argument block of every kernel outside the step family opens with: the world, the
+// batch, the draw key and the bound state (host.h's env_args fills it from an se_env). A kernel's
+// own arguments derive from it.
+struct EnvArgs {
+    const uint32_t* world;
+    WorldDims dims;
+    int64_t n, env_base;
+    uint64_t seed;
+    se_state st;
 };
 
 __device__ __forceinline__ Key env_key(uint64_t seed, int64_t env) {

@@ -1,5 +1,6 @@
 // host.h — what every handle's host half shares: the error text, HIP_TRY, the device guard,
-// device blocks that grow and their release, the dynamic-LDS opt-in and the entry checks.
+// device blocks that grow and their release, the dynamic-LDS opt-in, the entry checks and
+// env_args, the head of a kernel's argument block.
 //
 // A fragment of shipenv.hip's translation unit, included after se_env inside the host side's
 // anonymous namespace; it uses kBlock and kMaxBlocks from above it. No device code.
@@ -100,4 +101,11 @@ int check_ready(se_env* env) {
     if (!env) return fail(SE_EINVAL, "null env");
     if (!env->bound) return fail(SE_ESTATE, "se_bind has not been called");
     return SE_OK;
+}
+
+// ---------------------------------------------------------------- kernel arguments
+// The head of a kernel's argument block (EnvArgs, env_core.h): an entry point assigns it once
+// and then the kernel's own fields.
+EnvArgs env_args(const se_env* env) {
+    return EnvArgs{env->d_world, env->dims, env->n, env->env_base, env->seed, env->st};
 }

@@ -5,9 +5,9 @@
 //
 // A fragment of shipenv.hip's translation unit, included at its end after qpolicy.h and nav.h:
 // not a stand-alone header. Uses world.h (WorldDims, LdsWorld, stage_world, sqrt_rn), env_core.h
-// (Ship, Pending, env_key), rollout.h (sample_action, drawn_step, rollout_run), nav.h (NavTables,
-// nav_playout, se_nav, nav_ready), philox.h, and the host side's se_env, check_ready, fail,
-// HIP_TRY, DeviceGuard, aligned16, device_free and world_lds (host.h).
+// (EnvArgs, Ship, load_ship, Pending, env_key), rollout.h (sample_action, drawn_step, rollout_run),
+// nav.h (NavTables, nav_playout, se_nav, nav_ready), philox.h, and the host side's se_env, env_args,
+// check_ready, fail, HIP_TRY, DeviceGuard, aligned16, device_free and world_lds (host.h).
 //
 // One lane runs choose_action for one env: S = num_simulations sequential simulations
 // (selection by UCB1, one expansion, a random rollout, backpropagation) on a private Ship
@@ -94,14 +94,10 @@ __device__ __forceinline__ void mcts_action(const LdsWorld& w, uint32_t node, in
     }
 }
 
-struct MctsArgs {
-    const uint32_t* world;
-    WorldDims dims;
-    int64_t n, env_base, mcts_base;
-    uint64_t seed;
+struct MctsArgs : EnvArgs {
+    int64_t mcts_base;
     int32_t sims, max_steps, max_attempts;
     double c;
-    se_state st;
     const double* logtab;  // [sims + 1]: log(v) from the host's C library, v >= 1
     int4* rec;             // [sims + 1][n]: node word, index into the parent's possible actions, visits, 0
     double* total;         // [sims + 1][n]
@@ -220,7 +216,7 @@ __global__ __launch_bounds__(kMctsBlock) void mcts_kernel(typename Playout::Args
     const int S = A.sims;
     for (int64_t i = (int64_t)blockIdx.x * kMctsBlock + threadIdx.x; i < A.n;
          i += (int64_t)gridDim.x * kMctsBlock) {
-        const Ship s0{A.st.x[i], A.st.y[i], A.st.fuel[i], A.st.cargo[i], A.st.origin[i], A.st.dest[i]};
+        const Ship s0 = load_ship(A.st, i);
         const int64_t id0 = A.mcts_base + (A.env_base + i) * S;
         const uint32_t root = mcts_pack(kMctsNoParent, s0);  // root = MCTSNode(state) (:253)
         A.rec[i] = make_int4((int)root, 0, 0, 0);
@@ -401,17 +397,12 @@ int mcts_launch(se_mcts* m, int32_t simulations, double c_param, int32_t max_rol
     if (rc) return rc;
     const size_t nodes = (size_t)(m->max_sims + 1) * (size_t)m->n;
     typename Playout::Args A{};
-    A.world = env->d_world;
-    A.dims = env->dims;
-    A.n = env->n;
-    A.env_base = env->env_base;
+    static_cast<EnvArgs&>(A) = env_args(env);
     A.mcts_base = mcts_base;
-    A.seed = env->seed;
     A.sims = simulations;
     A.max_steps = max_rollout_steps;
     A.max_attempts = max_attempts;
     A.c = c_param;
-    A.st = env->st;
     A.logtab = m->d_log;
     A.rec = reinterpret_cast<int4*>(m->d_tree);
     A.total = reinterpret_cast<double*>(m->d_tree + 16 * nodes);

@@ -2,19 +2,19 @@
 // nav.h — the navigator (an extension: the reference has no such component): the expert policy
 // nav_action on the route tables of navfield.h, the two kernels that run it (se_nav_actions on
 // the env's state, se_rollout_nav on private copies), and the se_nav handle that builds the
-// tables on the host and keeps them on the device; and nav_playout, the rollout's loop for one
-// lane, which the MCTS decision kernel plays as its playout.
+// tables on the host and keeps them on the device; and nav_playout, the rollout's positions for
+// one lane, which the MCTS decision kernel plays as its playout.
 //
 // A fragment of shipenv.hip's translation unit, included at its end before mcts.h (whose
 // se_mcts_choose_nav plays nav_playout below): not a stand-alone header.
-// Uses world.h (WorldDims, LdsWorld, world_view, stage_world), env_core.h (Ship, Pending,
-// env_key), rollout.h (drawn_step), philox.h, navfield.h, and the host side's se_env, check_ready,
-// fail, HIP_TRY, DeviceGuard, device_reserve, device_free, world_lds, aligned16 (host.h) and
-// grid_for.
+// Uses world.h (WorldDims, LdsWorld, world_view, stage_world), env_core.h (EnvArgs, Ship,
+// load_ship, Pending), rollout.h (drawn_step), episode.h (EpisodeArgs, episode_lane, EpisodeTally,
+// episode_store), philox.h, navfield.h, and the host side's se_env, env_args, check_ready, fail,
+// HIP_TRY, DeviceGuard, device_reserve, device_free, world_lds, aligned16 (host.h) and grid_for.
 //
-// The policy and the draw contract are stated in include/shipenv.h. The rollout is plan.h's loop
-// with nav_action where plan_load stood: position k draws what se_rollout_plan's position k
-// draws, so a navigated rollout equals the scripted rollout of the actions it emitted.
+// The policy and the draw contract are stated in include/shipenv.h. The rollout is episode.h's
+// scaffold, as se_rollout_plan is, around nav_position: position k draws what se_rollout_plan's
+// position k draws, so a navigated rollout equals the scripted rollout of the actions it emitted.
 //
 // The dir byte is read from global memory: one dependent byte per step and lane out of a table
 // of P * H * W bytes (50 KB at the default world), which stays in L2. Staging the table in LDS
@@ -88,20 +88,41 @@ __device__ __forceinline__ int32_t nav_agent_index(int P, const NavAction& act) 
     return act.a <= 199 ? 54 + P + act.a : -1;
 }
 
-// se_rollout_nav's loop for one lane, position for position and draw for draw: the navigator
+// Position k of a navigated rollout on the private ship s under `key`: the navigator's action,
+// stepped by drawn_step on the blocks (k, slot 12) and (k, slot 13). On any status but SE_NAV_OK
+// the navigator had no action: nothing was drawn or stepped, and p holds nothing. Both the
+// rollout kernel and the playout below are made of this. (The step comes back by value: handed
+// out through a reference, the rollout kernel's step loop compiled 28 instructions longer.)
+struct NavStep {
+    int32_t status;  // SE_NAV_*
+    Pending p;
+};
+
+__device__ __forceinline__ NavStep nav_position(const LdsWorld& w, const NavTables& t, Ship& s, const Key& key,
+                                                int32_t k, double refuel_below, int32_t load) {
+    const NavAction act = nav_action(w, t, s, refuel_below, load);
+    NavStep r;
+    r.status = act.status;
+    if (act.status == SE_NAV_OK) {
+        const U4 d = draw(key, (uint32_t)k, kSlotRollout);
+        r.p = drawn_step(w, s, key, (uint32_t)k, kSlotRolloutB, d, act.ty, act.a, act.b);
+    }
+    return r;
+}
+
+// se_rollout_nav's positions for one lane, position for position and draw for draw: the navigator
 // played on the private ship s for at most `steps` positions under `key`, the counted steps'
 // rewards summed in order into total. A raising step is skipped and not counted (by the policy's
 // construction there is none); a counted step that reports done ends it. False where the
 // navigator had no action at some position ("stuck"): total is what was summed until then.
-// The playout of se_mcts_choose_nav (mcts.h); nav_rollout_kernel keeps its wave-ballot loop.
+// The playout of se_mcts_choose_nav (mcts.h).
 __device__ __forceinline__ bool nav_playout(const LdsWorld& w, const NavTables& t, Ship& s, const Key& key,
                                             int32_t steps, double refuel_below, int32_t load, double& total) {
     total = 0.0;
     for (int32_t k = 0; k < steps; ++k) {
-        const NavAction act = nav_action(w, t, s, refuel_below, load);
-        if (act.status != SE_NAV_OK) return false;
-        const U4 d = draw(key, (uint32_t)k, kSlotRollout);
-        const Pending p = drawn_step(w, s, key, (uint32_t)k, kSlotRolloutB, d, act.ty, act.a, act.b);
+        const NavStep st = nav_position(w, t, s, key, k, refuel_below, load);
+        if (st.status != SE_NAV_OK) return false;
+        const Pending& p = st.p;
         if (p.e != SE_ERR_OK) continue;
         total += p.r;
         if (p.dead) break;
@@ -109,11 +130,7 @@ __device__ __forceinline__ bool nav_playout(const LdsWorld& w, const NavTables& 
     return true;
 }
 
-struct NavActionsArgs {
-    const uint32_t* world;
-    WorldDims dims;
-    int64_t n;
-    se_state st;
+struct NavActionsArgs : EnvArgs {  // env_base and seed are not read: the policy draws nothing
     NavTables tab;
     double refuel_below;
     int32_t load;
@@ -126,7 +143,7 @@ struct NavActionsArgs {
 __global__ __launch_bounds__(kBlock) void nav_actions_kernel(NavActionsArgs A) {
     const LdsWorld w = world_view(A.dims, A.world);
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * kBlock) {
-        const Ship s{A.st.x[i], A.st.y[i], A.st.fuel[i], A.st.cargo[i], A.st.origin[i], A.st.dest[i]};
+        const Ship s = load_ship(A.st, i);
         int32_t dist;
         const NavAction act = nav_action<true>(w, A.tab, s, A.refuel_below, A.load, &dist);
         A.type[i] = act.ty;
@@ -138,87 +155,47 @@ __global__ __launch_bounds__(kBlock) void nav_actions_kernel(NavActionsArgs A) {
     }
 }
 
-struct NavRolloutArgs {
-    const uint32_t* world;
-    WorldDims dims;
-    int64_t n, m, rollout_base;
-    uint64_t seed;
+struct NavRolloutArgs : EpisodeArgs {
     int32_t steps;
-    se_state st;
-    const int32_t* src;
-    const int64_t* ids;
     NavTables tab;
     double refuel_below;
     int32_t load;
-    double* ret;
-    int32_t* counted;
-    int32_t* status;
     se_nav_out out;  // null pointers: not wanted
 };
 
-// plan_kernel's loop: one lane per rollout, the waves in a grid-stride loop with the world
-// staged once per workgroup; the step loop ends when no lane of the wave is still playing.
+// One lane per rollout, the waves in a grid-stride loop with the world staged once per
+// workgroup; the step loop ends when no lane of the wave is still playing. A position where the
+// navigator has no action ends the lane's rollout as stuck.
 __global__ __launch_bounds__(kBlock) void nav_rollout_kernel(NavRolloutArgs A) {
     extern __shared__ uint32_t lds[];
     const LdsWorld w = stage_world(A.world, A.dims, lds);
     const int lane = (int)(threadIdx.x & 63u);
     for (int64_t r0 = (int64_t)blockIdx.x * kBlock + (int64_t)(threadIdx.x & ~63u); r0 < A.m;
          r0 += (int64_t)gridDim.x * kBlock) {
-        const int64_t r = r0 + lane;
-        const bool in = r < A.m;
-        const int64_t i = in ? (int64_t)A.src[r] : -1;
-        const bool good = in & (i >= 0) & (i < A.n);
-        const int64_t ic = good ? i : 0;  // an in-range index for the state loads
-        Ship s{-1, -1, 0.0, -1, SE_NONE, SE_NONE};  // what a bad source reports
-        if (good) s = Ship{A.st.x[ic], A.st.y[ic], A.st.fuel[ic], A.st.cargo[ic], A.st.origin[ic], A.st.dest[ic]};
-        const Key key = env_key(A.seed, (good && A.ids) ? A.ids[r] : A.rollout_base + r);
-        double total = 0.0;
-        int32_t counted = 0, raised = 0, first_err = SE_ERR_OK, first_at = -1;
+        EpisodeLane L = episode_lane(A, r0 + lane);
+        EpisodeTally T(L);
         int32_t arrivals = 0, nav_status = SE_NAV_OK, stuck_at = -1;
-        int32_t status = good ? SE_PLAN_END : SE_PLAN_BAD_SRC;
-        bool alive = good & (A.steps > 0);
+        bool alive = L.good & (A.steps > 0);
         for (int32_t k = 0; __ballot(alive) != 0ull; ++k) {
             if (alive) {
-                const NavAction act = nav_action(w, A.tab, s, A.refuel_below, A.load);
-                if (act.status != SE_NAV_OK) {
-                    status = SE_PLAN_STUCK;
-                    nav_status = act.status;
+                const NavStep st = nav_position(w, A.tab, L.s, L.key, k, A.refuel_below, A.load);
+                if (st.status != SE_NAV_OK) {
+                    T.status = SE_PLAN_STUCK;
+                    nav_status = st.status;
                     stuck_at = k;
                     alive = false;
                 } else {
-                    const U4 d = draw(key, (uint32_t)k, kSlotRollout);
-                    const Pending p = drawn_step(w, s, key, (uint32_t)k, kSlotRolloutB, d, act.ty, act.a, act.b);
-                    if (p.e != SE_ERR_OK) {
-                        first_at = raised == 0 ? k : first_at;
-                        first_err = raised == 0 ? p.e : first_err;
-                        raised += 1;
-                    } else {
-                        total += p.r;
-                        counted += 1;
-                        arrivals += p.arrive ? 1 : 0;
-                        status = p.dead ? SE_PLAN_DONE : status;
-                    }
-                    alive = (status != SE_PLAN_DONE) & (k + 1 < A.steps);
+                    T.add(st.p, k);
+                    arrivals += st.p.arrive ? 1 : 0;  // a raising step has none
+                    alive = !T.done() & (k + 1 < A.steps);
                 }
             }
         }
-        if (!in) continue;
-        A.ret[r] = total;
-        A.counted[r] = counted;
-        A.status[r] = status;
-        if (A.out.arrivals) A.out.arrivals[r] = arrivals;
-        if (A.out.nav_status) A.out.nav_status[r] = nav_status;
-        if (A.out.stuck_at) A.out.stuck_at[r] = stuck_at;
-        const se_plan_out& E = A.out.end;
-        if (E.raised) E.raised[r] = raised;
-        if (E.first_err) E.first_err[r] = first_err;
-        if (E.first_err_at) E.first_err_at[r] = first_at;
-        if (E.x) E.x[r] = s.x;
-        if (E.y) E.y[r] = s.y;
-        if (E.fuel) E.fuel[r] = s.fuel;
-        if (E.cargo) E.cargo[r] = s.cargo;
-        if (E.origin) E.origin[r] = s.origin == SE_NONE ? -1 : s.origin;
-        if (E.dest) E.dest[r] = s.dest == SE_NONE ? -1 : s.dest;
+        if (!L.in) continue;
+        episode_store(A, A.out.end, L, T);
+        if (A.out.arrivals) A.out.arrivals[L.r] = arrivals;
+        if (A.out.nav_status) A.out.nav_status[L.r] = nav_status;
+        if (A.out.stuck_at) A.out.stuck_at[L.r] = stuck_at;
     }
 }
 
@@ -336,10 +313,7 @@ int se_nav_actions(se_nav* h, double refuel_below, int32_t load, int32_t* type, 
     if (!type || !a || !b || !status) return fail(SE_EINVAL, "null output pointer");
     DeviceGuard g(env->device);
     NavActionsArgs A{};
-    A.world = env->d_world;
-    A.dims = env->dims;
-    A.n = env->n;
-    A.st = env->st;
+    static_cast<EnvArgs&>(A) = env_args(env);
     A.tab = NavTables{h->d_field, h->d_dir};
     A.refuel_below = refuel_below;
     A.load = load;
@@ -380,22 +354,11 @@ int se_rollout_nav(se_nav* h, const int32_t* src, int64_t m, int32_t steps, doub
     rc = world_lds<nav_rollout_kernel>(env, lds);
     if (rc) return rc;
     NavRolloutArgs A{};
-    A.world = env->d_world;
-    A.dims = env->dims;
-    A.n = env->n;
-    A.m = m;
-    A.rollout_base = rollout_base;
-    A.seed = env->seed;
+    static_cast<EpisodeArgs&>(A) = {env_args(env), m, rollout_base, src, ids, ret, counted, status};
     A.steps = steps;
-    A.st = env->st;
-    A.src = src;
-    A.ids = ids;
     A.tab = NavTables{h->d_field, h->d_dir};
     A.refuel_below = refuel_below;
     A.load = load;
-    A.ret = ret;
-    A.counted = counted;
-    A.status = status;
     if (out) A.out = *out;
     nav_rollout_kernel<<<grid_for(m), kBlock, lds, (hipStream_t)stream>>>(A);
     HIP_TRY(hipGetLastError());

@@ -106,12 +106,7 @@ __global__ __launch_bounds__(kBlock) void replay_end_kernel(RecordArgs A) {
             const U4 o = draw(env_key(A.seed, A.env_base + i), A.epoch, kSlotExplicitReset);
             Ship s;
             reset_ship(w, s, o.v[0], o.v[1]);
-            A.st.x[i] = (uint8_t)s.x;
-            A.st.y[i] = (uint8_t)s.y;
-            A.st.fuel[i] = s.fuel;
-            A.st.cargo[i] = s.cargo;
-            A.st.origin[i] = (uint8_t)s.origin;
-            A.st.dest[i] = (uint8_t)s.dest;
+            store_ship(A.st, i, s);
             if (A.st.ep_return) A.st.ep_return[i] = 0.0f;
             if (A.st.ep_start) A.st.ep_start[i] = (int32_t)A.t;
             A.st.done[i] = 0;
@@ -176,12 +171,7 @@ __global__ __launch_bounds__(kBlock) void replay_end4_kernel(RecordArgs A) {
             const U4 o = draw(env_key(A.seed, A.env_base + i), A.epoch, kSlotExplicitReset);
             Ship sh;
             reset_ship(w, sh, o.v[0], o.v[1]);
-            A.st.x[i] = (uint8_t)sh.x;
-            A.st.y[i] = (uint8_t)sh.y;
-            A.st.fuel[i] = sh.fuel;
-            A.st.cargo[i] = sh.cargo;
-            A.st.origin[i] = (uint8_t)sh.origin;
-            A.st.dest[i] = (uint8_t)sh.dest;
+            store_ship(A.st, i, sh);
             if (A.st.ep_return) A.st.ep_return[i] = 0.0f;
             if (A.st.ep_start) A.st.ep_start[i] = (int32_t)A.t;
             A.st.done[i] = 0;

@@ -6,8 +6,8 @@
 //
 // A fragment of shipenv.hip's translation unit, included inside its anonymous
 // namespace where this text stood: not a stand-alone header.
-// Uses world.h (LdsWorld, stage_world, world_view) and env_core.h (Ship, Pending,
-// env_begin / env_finish, env_key, beta_part).
+// Uses world.h (LdsWorld, stage_world, world_view) and env_core.h (EnvArgs, Ship, load_ship,
+// Pending, env_begin / env_finish, env_key, beta_part).
 
 // ------------------------------------------------------------------ random policy
 // sample_action() (environment.py:245-263) on one env from one Philox word r.
@@ -37,13 +37,8 @@ __device__ __forceinline__ void sample_action(const LdsWorld& w, const Ship& s, 
     }
 }
 
-struct SampleArgs {
-    const uint32_t* world;
-    WorldDims dims;
-    int64_t n, env_base;
-    uint64_t seed;
+struct SampleArgs : EnvArgs {
     uint32_t t;
-    se_state st;
     int32_t* type;
     int32_t* a;
     int32_t* b;
@@ -55,7 +50,7 @@ __global__ __launch_bounds__(kBlock) void sample_kernel(SampleArgs A) {
     const LdsWorld w = world_view(A.dims, A.world);
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n;
          i += (int64_t)gridDim.x * kBlock) {
-        const Ship s{A.st.x[i], A.st.y[i], A.st.fuel[i], A.st.cargo[i], A.st.origin[i], A.st.dest[i]};
+        const Ship s = load_ship(A.st, i);
         const U4 d = draw(env_key(A.seed, A.env_base + i), A.t, kSlotSample);
         int ty, va, vb;
         sample_action(w, s, d.v[0], ty, va, vb);
@@ -69,13 +64,9 @@ __global__ __launch_bounds__(kBlock) void sample_kernel(SampleArgs A) {
 // src[r], then sample_action + step until done / max_steps counted steps /
 // max_attempts attempts. A raising step is retried without counting (:231-233);
 // a raising sample_action ends the rollout (it sits outside the try, :227).
-struct RolloutArgs {
-    const uint32_t* world;
-    WorldDims dims;
-    int64_t n, m, rollout_base;
-    uint64_t seed;
+struct RolloutArgs : EnvArgs {
+    int64_t m, rollout_base;
     int32_t max_steps, max_attempts;
-    se_state st;
     const int32_t* src;
     double* ret;
     int32_t* steps;
@@ -155,7 +146,7 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(RolloutArgs A) {
             A.status[r] = SE_ROLL_BAD_SRC;
             continue;
         }
-        Ship s{A.st.x[i], A.st.y[i], A.st.fuel[i], A.st.cargo[i], A.st.origin[i], A.st.dest[i]};
+        Ship s = load_ship(A.st, i);
         double total;
         int32_t steps;
         int sample_type;

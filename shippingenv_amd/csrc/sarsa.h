@@ -4,10 +4,10 @@
 // vector step, and se_sarsa_create / _layout / _bind / _step / _choose / _destroy.
 //
 // A fragment of shipenv.hip's translation unit, included at its end after mcts.h: not a
-// stand-alone header. Uses world.h (WorldDims, LdsWorld, stage_world), env_core.h (Ship,
-// Pending, env_key, u32, reset_ship), rollout.h (sample_action, drawn_step), philox.h, and the
-// host side's se_env, check_ready, fail, HIP_TRY, DeviceGuard, device_free, world_lds (host.h)
-// and grid_for.
+// stand-alone header. Uses world.h (WorldDims, LdsWorld, stage_world), env_core.h (EnvArgs, Ship,
+// load_ship / store_ship, Pending, env_key, u32, reset_ship), rollout.h (sample_action,
+// drawn_step), philox.h, and the host side's se_env, env_args, check_ready, fail, HIP_TRY,
+// DeviceGuard, device_free, world_lds (host.h) and grid_for.
 //
 // One vector step runs the body of train's inner loop (:255-272) for every env:
 //   * a fresh env (after a reset, or restarted by the previous vector step) first takes
@@ -163,13 +163,8 @@ __device__ __forceinline__ void sarsa_choose(const LdsWorld& w, const double* __
     sarsa_action(w.P, cmax, best, type, a, b);
 }
 
-struct SarsaArgs {
-    const uint32_t* world;
-    WorldDims dims;
-    int64_t n, env_base;
-    uint64_t seed;
+struct SarsaArgs : EnvArgs {
     uint32_t t;
-    se_state st;
     se_sarsa_state ag;
     const double* q;
     uint32_t* owner;
@@ -193,7 +188,7 @@ __global__ __launch_bounds__(kBlock) void sarsa_step_kernel(SarsaArgs A) {
     extern __shared__ uint32_t lds[];
     const LdsWorld w = stage_world(A.world, A.dims, lds);
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * kBlock) {
-        Ship s{A.st.x[i], A.st.y[i], A.st.fuel[i], A.st.cargo[i], A.st.origin[i], A.st.dest[i]};
+        Ship s = load_ship(A.st, i);
         int ty = A.ag.type[i], va = A.ag.a[i], vb = A.ag.b[i];
         int32_t ep_len = A.ag.ep_len[i];
         double ep_ret = A.ag.ep_return[i];
@@ -265,12 +260,7 @@ __global__ __launch_bounds__(kBlock) void sarsa_step_kernel(SarsaArgs A) {
             ep_len = 0;
             ep_ret = 0.0;
         }
-        A.st.x[i] = (uint8_t)s.x;
-        A.st.y[i] = (uint8_t)s.y;
-        A.st.fuel[i] = s.fuel;
-        A.st.cargo[i] = s.cargo;
-        A.st.origin[i] = (uint8_t)s.origin;
-        A.st.dest[i] = (uint8_t)s.dest;
+        store_ship(A.st, i, s);
         A.ag.type[i] = ty;
         A.ag.a[i] = va;
         A.ag.b[i] = vb;
@@ -294,13 +284,8 @@ __global__ __launch_bounds__(kBlock) void sarsa_commit_kernel(int64_t n, const i
     }
 }
 
-struct SarsaChooseArgs {
-    const uint32_t* world;
-    WorldDims dims;
-    int64_t n, env_base;
-    uint64_t seed;
+struct SarsaChooseArgs : EnvArgs {
     uint32_t t;
-    se_state st;
     const double* q;
     int32_t A, cmax;
     double epsilon;
@@ -313,7 +298,7 @@ __global__ __launch_bounds__(kBlock) void sarsa_choose_kernel(SarsaChooseArgs A)
     extern __shared__ uint32_t lds[];
     const LdsWorld w = stage_world(A.world, A.dims, lds);
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * kBlock) {
-        const Ship s{A.st.x[i], A.st.y[i], A.st.fuel[i], A.st.cargo[i], A.st.origin[i], A.st.dest[i]};
+        const Ship s = load_ship(A.st, i);
         const U4 c = draw(env_key(A.seed, A.env_base + i), A.t, kSlotSarsa);
         int ty, va, vb;
         sarsa_choose(w, A.q, A.A, A.cmax, s, A.epsilon, c.v[2], c.v[3], ty, va, vb);
@@ -438,13 +423,8 @@ int se_sarsa_step(se_sarsa* h, double lr, double gamma, double epsilon, int32_t 
     rc = world_lds<sarsa_step_kernel>(env, lds);
     if (rc) return rc;
     SarsaArgs A{};
-    A.world = env->d_world;
-    A.dims = env->dims;
-    A.n = env->n;
-    A.env_base = env->env_base;
-    A.seed = env->seed;
+    static_cast<EnvArgs&>(A) = env_args(env);
     A.t = t;
-    A.st = env->st;
     A.ag = h->ag;
     A.q = h->q;
     A.owner = h->d_owner;
@@ -485,8 +465,7 @@ int se_sarsa_choose(se_sarsa* h, double epsilon, uint32_t t, int32_t* type, int3
     size_t lds;
     rc = world_lds<sarsa_choose_kernel>(env, lds);
     if (rc) return rc;
-    const SarsaChooseArgs A{env->d_world, env->dims, env->n, env->env_base, env->seed, t, env->st,
-                            h->q, h->A, h->cmax, epsilon, type, a, b};
+    const SarsaChooseArgs A{env_args(env), t, h->q, h->A, h->cmax, epsilon, type, a, b};
     sarsa_choose_kernel<<<grid_for(env->n), kBlock, lds, (hipStream_t)stream>>>(A);
     HIP_TRY(hipGetLastError());
     return SE_OK;

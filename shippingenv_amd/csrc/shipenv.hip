@@ -76,7 +76,8 @@ constexpr double kMaxCargo = 50.0;
 #include "step_seq.h"     // step_group_state, step_seq_kernel, step_tail_seq_kernel
 #include "views.h"        // done-list copy, reset, observe, valid masks, gen_actions
 #include "rollout.h"      // random policy, rollouts, episode statistics
-#include "plan.h"         // scripted rollouts: the rollout loop with its actions read from memory
+#include "episode.h"      // the rollout scaffold: the lane, the tally and the store of its results
+#include "plan.h"         // scripted rollouts: the scaffold with its actions read from memory
 }  // namespace
 
 // ====================================================================== host side
@@ -682,7 +683,7 @@ int se_sample_actions(se_env* env, int32_t* type, int32_t* a, int32_t* b, uint32
     if (env->n == 0) return SE_OK;
     if (!type || !a || !b) return fail(SE_EINVAL, "null output pointer");
     DeviceGuard g(env->device);
-    SampleArgs A{env->d_world, env->dims, env->n, env->env_base, env->seed, t, env->st, type, a, b};
+    const SampleArgs A{env_args(env), t, type, a, b};
     sample_kernel<<<grid_for(env->n), kBlock, 0, (hipStream_t)stream>>>(A);
     HIP_TRY(hipGetLastError());
     return SE_OK;
@@ -697,20 +698,7 @@ int se_rollout(se_env* env, const int32_t* src, int64_t m, int32_t max_steps, in
     if (m > 0 && (!src || !ret || !steps || !status)) return fail(SE_EINVAL, "null rollout buffer");
     if (m == 0) return SE_OK;
     DeviceGuard g(env->device);
-    RolloutArgs A{};
-    A.world = env->d_world;
-    A.dims = env->dims;
-    A.n = env->n;
-    A.m = m;
-    A.rollout_base = rollout_base;
-    A.seed = env->seed;
-    A.max_steps = max_steps;
-    A.max_attempts = max_attempts;
-    A.st = env->st;
-    A.src = src;
-    A.ret = ret;
-    A.steps = steps;
-    A.status = status;
+    const RolloutArgs A{env_args(env), m, rollout_base, max_steps, max_attempts, src, ret, steps, status};
     rollout_kernel<<<grid_for(m), kBlock, lds_bytes(env), (hipStream_t)stream>>>(A);
     HIP_TRY(hipGetLastError());
     return SE_OK;
@@ -739,24 +727,13 @@ int se_rollout_plan(se_env* env, const int32_t* src, int64_t m, const int32_t* t
     rc = agent ? world_lds<plan_kernel<true>>(env, lds) : world_lds<plan_kernel<false>>(env, lds);
     if (rc) return rc;
     PlanArgs A{};
-    A.world = env->d_world;
-    A.dims = env->dims;
-    A.n = env->n;
-    A.m = m;
+    static_cast<EpisodeArgs&>(A) = {env_args(env), m, rollout_base, src, ids, ret, counted, status};
     A.ld = ld;
-    A.rollout_base = rollout_base;
-    A.seed = env->seed;
     A.steps = steps;
-    A.st = env->st;
-    A.src = src;
     A.type = type;
     A.a = a;
     A.b = b;
     A.len = len;
-    A.ids = ids;
-    A.ret = ret;
-    A.counted = counted;
-    A.status = status;
     if (out) A.out = *out;
     const auto kernel = agent ? plan_kernel<true> : plan_kernel<false>;
     kernel<<<grid_for(m), kBlock, lds, (hipStream_t)stream>>>(A);
@@ -880,16 +857,11 @@ int se_host_step_replay(se_host* h, int64_t n, const se_state* st, const int32_t
         return fail(SE_EINVAL, "null state, action or tape buffer");
     const LdsWorld w = world_view(h->dims, h->img.data());
     for (int64_t i = 0; i < n; ++i) {
-        Ship s{st->x[i], st->y[i], st->fuel[i], st->cargo[i], st->origin[i], st->dest[i]};
+        Ship s = load_ship(*st, i);
         Pending p;
         se_tape* tp = tape + i;
         tp->used = (int32_t)replay_env(w, s, p, SE_ERR_OK, type[i], a[i], b[i], tp->u_fuel, tp->u_gate, tp);
-        st->x[i] = (uint8_t)s.x;
-        st->y[i] = (uint8_t)s.y;
-        st->fuel[i] = s.fuel;
-        st->cargo[i] = s.cargo;
-        st->origin[i] = (uint8_t)s.origin;
-        st->dest[i] = (uint8_t)s.dest;
+        store_ship(*st, i, s);
         st->reward[i] = (float)p.r;  // one rounding of the reference's f64 reward
         st->done[i] = (uint8_t)p.dead;
         st->err[i] = (int8_t)p.e;

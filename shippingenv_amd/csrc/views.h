@@ -77,12 +77,7 @@ __device__ __forceinline__ void reset_env(const ResetArgs& A, const LdsWorld& w,
             const U4 o = draw(env_key(A.seed, A.env_base + i), A.epoch, kSlotExplicitReset);
             reset_ship(w, s, o.v[0], o.v[1]);
         }
-        A.st.x[i] = (uint8_t)s.x;
-        A.st.y[i] = (uint8_t)s.y;
-        A.st.fuel[i] = s.fuel;
-        A.st.cargo[i] = s.cargo;
-        A.st.origin[i] = (uint8_t)s.origin;
-        A.st.dest[i] = (uint8_t)s.dest;
+        store_ship(A.st, i, s);
         if (A.st.ep_return) A.st.ep_return[i] = 0.0f;
         if (A.st.ep_start) A.st.ep_start[i] = (int32_t)A.t;
         A.st.done[i] = 0;

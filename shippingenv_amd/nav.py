@@ -170,21 +170,13 @@ class VecNavigator:
         m = src.numel()
         s = env._dev(src, torch.int32, count=m)
         idt = None if ids is None else env._dev(ids, torch.int64, count=m)
-        kw = dict(dtype=torch.int32, device=env.device)
-        ret = torch.empty(m, dtype=torch.float64, device=env.device)
-        steps_t, status, arrivals, nav_status, stuck_at, raised, first_err, first_at = (
-            torch.empty(m, **kw) for _ in range(8))
-        end = (None,) * 6
-        if return_end:
-            end = tuple(torch.empty(m, dtype=torch.float64 if f == "fuel" else torch.int32, device=env.device)
-                        for f in ("x", "y", "fuel", "cargo", "origin", "dest"))
-        addr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        out = N.SeNavOut(addr(arrivals), addr(nav_status), addr(stuck_at),
-                         N.SePlanOut(*[addr(t) for t in (raised, first_err, first_at) + end]))
+        # own: arrivals, nav_status, stuck_at
+        ret, (steps_t, status), own, noted, end, plan_out = env._episode_outputs(m, return_end, extra=3)
+        out = N.SeNavOut(*[t.data_ptr() for t in own], plan_out)
         self._call(N.lib().se_rollout_nav, _ptr(s), m, int(steps), self.refuel_below, self.load, _ptr(idt),
                    int(rollout_base), _ptr(ret), _ptr(steps_t), _ptr(status), C.byref(out), env._stream())
         self._keep = (s, idt)
-        return NavResult(ret, steps_t, status, arrivals, nav_status, stuck_at, raised, first_err, first_at, *end)
+        return NavResult(ret, steps_t, status, *own, *noted, *end)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

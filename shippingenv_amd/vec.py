@@ -389,19 +389,26 @@ class VecEnv:
         ld = rows[0].stride(0) if K > 1 and m > 0 else (m + 3) // 4 * 4
         ln = None if lengths is None else self._dev(lengths, torch.int32, count=m)
         idt = None if ids is None else self._dev(ids, torch.int64, count=m)
-        kw = dict(dtype=torch.int32, device=self.device)
-        ret = torch.empty(m, dtype=torch.float64, device=self.device)
-        steps, status, raised, first_err, first_at = (torch.empty(m, **kw) for _ in range(5))
-        end = (None,) * 6
-        if return_end:
-            end = tuple(torch.empty(m, dtype=torch.float64 if f == "fuel" else torch.int32, device=self.device)
-                        for f in ("x", "y", "fuel", "cargo", "origin", "dest"))
-        out = N.SePlanOut(*[None if t is None else t.data_ptr() for t in (raised, first_err, first_at) + end])
+        ret, (steps, status), _, noted, end, out = self._episode_outputs(m, return_end)
         N.check(N.lib().se_rollout_plan(self._h, _ptr(s), m, _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]), ld, K,
                                         _ptr(ln), _ptr(idt), int(rollout_base), _ptr(ret), _ptr(steps),
                                         _ptr(status), C.byref(out), self._stream()))
         self._keep = (s, rows, ln, idt)
-        return PlanResult(ret, steps, status, raised, first_err, first_at, *end)
+        return PlanResult(ret, steps, status, *noted, *end)
+
+    def _episode_outputs(self, m, return_end, extra=0):
+        """Fresh outputs of m rollouts for se_rollout_plan and se_rollout_nav: ret (f64), (steps,
+        status), `extra` more int32 tensors for the caller's own outputs, (raised, first_err,
+        first_err_at), the end ship's six (x, y, fuel f64, cargo, origin, dest; None each without
+        return_end) and the SePlanOut that names those nine."""
+        ret = torch.empty(m, dtype=torch.float64, device=self.device)
+        ints = tuple(torch.empty(m, dtype=torch.int32, device=self.device) for _ in range(5 + extra))
+        end = (None,) * 6
+        if return_end:
+            end = tuple(torch.empty(m, dtype=torch.float64 if f == "fuel" else torch.int32, device=self.device)
+                        for f in ("x", "y", "fuel", "cargo", "origin", "dest"))
+        out = N.SePlanOut(*[None if t is None else t.data_ptr() for t in ints[-3:] + end])
+        return ret, ints[:2], ints[2:-3], ints[-3:], end, out
 
     def episode_stats(self):
         """Device f64[3] {sum of returns, episodes, sum of lengths} since the last clear."""
