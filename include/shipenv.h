@@ -177,6 +177,13 @@ int se_step(se_env* env, const int32_t* actions, void* stream);
  * behind the world image and the 2 KiB table of stocks by cell code); SHIPENV_SEQ_GATE_POOL=0
  * at se_create, or a world image that leaves no room for it under the 64 KiB of a launch,
  * draws it for every lane every step instead. The results are the same bits.
+ * A wave all of whose envs are inside the map and have a destination steps on a copy of the cell
+ * codes with a border of one cell around the map (LDS behind the pools; 10.2 KiB for a 100 x 100
+ * map): a move off the map reads the border's code, so such a step has no bounds test. Worlds
+ * of more than 253 ports, worlds whose table would leave fewer than four workgroups on a compute
+ * unit, and every world under SHIPENV_SEQ_RING=0 at se_create have no such table; their waves,
+ * and any wave with an env loaded outside the map or without a destination, run the general
+ * step. The results are the same bits.
  * SHIPENV_SEQ_FUSE=0 at se_create issues one se_step launch per step
  * instead (the same kernel code as se_step's under a trace name of its own). With
  * auto-reset the run is always a launch per step (done lists, statistics and episode

@@ -114,6 +114,7 @@ struct se_env {
     bool seq_fuse = true;   // se_step_seq without auto-reset: one launch per run (SHIPENV_SEQ_FUSE=0: one per step)
     int32_t seq_max_steps = 1024;  // steps of one fused launch at most (seq_max_steps)
     bool seq_gate_pool = true;  // the fused launch draws GATE through the wave's pool (SHIPENV_SEQ_GATE_POOL=0: draw2)
+    bool seq_ring = true;       // the fused launch's regular waves step on the bordered cell table (SHIPENV_SEQ_RING=0: none do)
 };
 
 // A host-resident world (se_host_*): no device, no HIP call. It steps envs whose SoA
@@ -129,8 +130,8 @@ namespace {
 #include "host.h"  // fail, HIP_TRY, DeviceGuard, device blocks, the LDS opt-in, check_ready
 
 // ---------------------------------------------------------------- launch-time switches
-// SHIPENV_STEP_BLOCKS, _DONE_PAD, _NT_LOADS, _SEQ_MAX_STEPS, _SEQ_FUSE, _SEQ_GATE_POOL and
-// _MASK_TILED: se_create resolves all seven, once, into the se_env, and a launch reads no
+// SHIPENV_STEP_BLOCKS, _DONE_PAD, _NT_LOADS, _SEQ_MAX_STEPS, _SEQ_FUSE, _SEQ_GATE_POOL, _SEQ_RING
+// and _MASK_TILED: se_create resolves all eight, once, into the se_env, and a launch reads no
 // environment variable.
 
 // Workgroup cap of the step kernel: each thread then walks ceil(groups / (cap*256))
@@ -191,6 +192,14 @@ bool seq_fuse() {
 // of the pool's measurements and tests. Results are the same bits either way.
 bool seq_gate_pool() {
     const char* v = getenv("SHIPENV_SEQ_GATE_POOL");
+    return !v || atoi(v) != 0;
+}
+
+// SHIPENV_SEQ_RING=0: the fused launch carries no bordered cell table (step_lean.h), so every wave
+// runs the general state-only step and draws directly (step_seq.h): the same-library control of
+// the table's measurements and tests. Results are the same bits either way.
+bool seq_ring() {
+    const char* v = getenv("SHIPENV_SEQ_RING");
     return !v || atoi(v) != 0;
 }
 
@@ -264,9 +273,14 @@ int upload_world(se_env* env, int32_t P, const int32_t* px, const int32_t* py, c
     std::vector<uint32_t> img;
     int rc = build_world_image(env->dims.H, env->dims.W, env->water, P, px, py, pf, pc, d, img);
     if (rc) return rc;
-    rc = device_reserve(env->d_world, env->world_cap, (size_t)d.padded() * 4);
+    // the bordered cell table of the fused step sequence's regular waves (step_lean.h) follows
+    // the image; no other kernel reads past the image
+    std::vector<uint8_t> ring(ring_table_bytes(d.H, d.W));
+    ring_table_build(d.H, d.W, reinterpret_cast<const uint8_t*>(img.data()), ring.data());
+    rc = device_reserve(env->d_world, env->world_cap, (size_t)d.padded() * 4 + ring.size());
     if (rc) return rc;
     HIP_TRY(hipMemcpy(env->d_world, img.data(), (size_t)d.padded() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(env->d_world + d.padded(), ring.data(), ring.size(), hipMemcpyHostToDevice));
     env->dims = d;
     env->port_x.assign(px, px + P);
     env->port_y.assign(py, py + P);
@@ -401,10 +415,14 @@ int launch_step_seq(se_env* env, const int32_t* act, int64_t ld, int32_t steps, 
         // leaves no room for the pools under the 64 KiB a launch can ask for draws directly.
         const size_t base = lds_bytes(env) + kStockByCodeBytes;
         const bool pool = env->seq_gate_pool && base + kGatePoolBytes <= kLdsDefault;
-        const size_t lds = base + (pool ? kGatePoolBytes : 0);
+        // then the bordered cell table, where the world has one and four workgroups still share a CU
+        const size_t without = base + (pool ? kGatePoolBytes : 0);
+        const uint32_t ring = env->seq_ring && ring_table_fits(env->dims.H, env->dims.W, env->dims.P, without)
+                                  ? ring_table_bytes(env->dims.H, env->dims.W) : 0u;
+        const size_t lds = without + ring;
         const auto kernel = pool ? (env->nt_loads ? step_seq_kernel<true, true> : step_seq_kernel<false, true>)
                                  : (env->nt_loads ? step_seq_kernel<true, false> : step_seq_kernel<false, false>);
-        kernel<<<env->grid, kStepBlock, lds, s>>>(A, steps, ld);
+        kernel<<<env->grid, kStepBlock, lds, s>>>(A, steps, ld, ring);
         HIP_TRY(hipGetLastError());
     }
     if (env->n & 3) {
@@ -491,6 +509,7 @@ int se_create(se_env** out, int device, int64_t n, int64_t env_id_base, int32_t 
         env->seq_fuse = seq_fuse();
         env->seq_max_steps = seq_max_steps();
         env->seq_gate_pool = seq_gate_pool();
+        env->seq_ring = seq_ring();
         env->mask_tiled = mask_tiled();
     }
     hipError_t e = hipMalloc(&env->d_slab, (size_t)env->nslab * 4 * sizeof(double));

@@ -1,8 +1,9 @@
 // step_lean.h — the state-only step's action decode and fuel update (step_seq.h,
 // step_group_state), as host + device helpers: tools/step_lean_check.cpp compares them on the
 // host with the forms they replaced (the error cascade's terms, the select of -scale / -0.0),
-// and tools/step_trim_check.cpp the move test on val, the fuel scale's FMA and the GATE pool's
-// window choice.
+// tools/step_trim_check.cpp the move test on val, the fuel scale's FMA and the GATE pool's
+// window choice, and tools/step_ring_check.cpp the regular step's decode on the bordered cell
+// table with the general form's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,6 +35,56 @@ __host__ __device__ __forceinline__ bool lean_do_move_val(int val, uint32_t boun
 __host__ __device__ __forceinline__ bool lean_sel_ok(int act, int P, bool same) {
     const bool is_sel = (uint32_t)act - 4u < (uint32_t)P;
     return is_sel & !same;
+}
+
+// The bordered cell table of the regular state-only step (step_seq.h, step_group_ring): the
+// map's cell codes with one ring of kRingBorder around them, (H + 2) x (W + 2) bytes, so the
+// target of any unit move from a cell of the map is a byte of the table and "off the map" is a
+// cell code like ground. A position is carried biased by one in both halves, (x + 1) | (y + 1)
+// << 16: its index in the table is (x + 1) (W + 2) + (y + 1), one dot product against
+// (W + 2) | 1 << 16, and v_pk_add_u16 of a unit move never wraps (x + 1 - 1 >= 0).
+// kRingBorder is 254: with kCellGround at 255, port 253's code in a world of 254 ports. So the
+// table exists for P <= kRingMaxPorts only, and only where the launch's LDS with it keeps four
+// workgroups on a CU (kRingLdsPerBlock: a quarter of the CU's 160 KiB), which is the launch's
+// occupancy without it.
+constexpr uint32_t kRingBorder = 254;
+constexpr uint32_t kRingGround = 255;  // world.h's kCellGround
+constexpr int kRingMaxPorts = 253;
+constexpr size_t kRingLdsPerBlock = 160 * 1024 / 4;
+constexpr uint32_t kRingBias = 0x00010001u;
+
+// bytes of the table, in whole 16-byte units (it is staged by 16-byte loads)
+__host__ __device__ __forceinline__ uint32_t ring_table_bytes(int H, int W) {
+    return ((uint32_t)(H + 2) * (uint32_t)(W + 2) + 15u) & ~15u;
+}
+// Does a launch whose other LDS is `lds_without` bytes carry the table?
+__host__ __device__ __forceinline__ bool ring_table_fits(int H, int W, int P, size_t lds_without) {
+    return P <= kRingMaxPorts && lds_without + ring_table_bytes(H, W) <= kRingLdsPerBlock;
+}
+// The table of an H x W map's cell codes (cell[x * W + y]) into ring_table_bytes(H, W) bytes;
+// the bytes past the last row are zero.
+__host__ __forceinline__ void ring_table_build(int H, int W, const uint8_t* cell, uint8_t* out) {
+    const uint32_t n = ring_table_bytes(H, W);
+    for (uint32_t i = 0; i < n; ++i) out[i] = i < (uint32_t)(H + 2) * (uint32_t)(W + 2) ? (uint8_t)kRingBorder : 0;
+    for (int x = 0; x < H; ++x)
+        for (int y = 0; y < W; ++y) out[(size_t)(x + 1) * (size_t)(W + 2) + (size_t)(y + 1)] = cell[(size_t)x * W + y];
+}
+// x | y << 16 (x, y < 256) to the biased form and back: no carry crosses the halves
+__host__ __device__ __forceinline__ uint32_t ring_bias(uint32_t p) { return p + kRingBias; }
+__host__ __device__ __forceinline__ uint32_t ring_unbias(uint32_t bp) { return bp - kRingBias; }
+// index of a biased position (or of a unit move's target from one) in the table
+__host__ __device__ __forceinline__ uint32_t ring_index(uint32_t bp, int W) {
+    return (bp & 0xffffu) * (uint32_t)(W + 2) + (bp >> 16);
+}
+// The regular step's decode from the target's code in the bordered table: a move that passed
+// its checks (the target is on the map; an env of a regular wave has a destination), and one
+// that changes the position (the target is no ground either). A move off the map is an error
+// and draws no gate; a move blocked by ground is a move.
+__host__ __device__ __forceinline__ bool ring_do_move(int val, uint32_t bound, uint32_t code) {
+    return ((uint32_t)val > bound) & (code != kRingBorder);
+}
+__host__ __device__ __forceinline__ bool ring_moved(int val, uint32_t bound, uint32_t code) {
+    return ((uint32_t)val > bound) & (code < kRingBorder);
 }
 
 // fuel - (moved ? scale : 0) with the bits of fuel + (moved ? -scale : -0.0): (-scale) * 1 is

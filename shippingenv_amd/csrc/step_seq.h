@@ -1,7 +1,8 @@
 #pragma once
 // step_seq.h — se_step_seq's fused run of steps with the state in registers:
-// Carried, the state-only step_group_state, stock_by_code, the GATE pool, step_seq_kernel and
-// the partial last group's step_tail_seq_kernel.
+// Carried, the state-only step_group_state and its regular form on the bordered cell table,
+// step_group_ring, stock_by_code, the GATE pool, step_seq_kernel and the partial last group's
+// step_tail_seq_kernel.
 //
 // A fragment of shipenv.hip's translation unit, included inside its anonymous
 // namespace where this text stood: not a stand-alone header.
@@ -32,9 +33,10 @@
 // (profiles/seq_guard/freq.json). The result says whether the take block ran (wave-uniform): the
 // only place where an env's cargo can become positive, which the caller's GATE pool needs.
 struct Carried {
-    uint32_t pos[4];  // x | y << 16
+    uint32_t pos[4];  // x | y << 16; in a regular wave (step_group_ring) biased: x + 1 | y + 1 << 16
     int org[4], dst[4];
     uint32_t code[4];   // the cell code under the ship, w.cell[cell_of(pos)]
+    bool near;          // step_group_ring: some env of the wave is on a non-water cell (wave-uniform)
     uint32_t thr[4];    // the gate threshold of the env's cargo, gate_thr_of(w, cargo)
     const int2* take;   // the block's stocks by cell code (stock_by_code), the same for every env
 };
@@ -54,6 +56,7 @@ template <bool kSched>
 struct SeqInv {
     KeySched ks;
     uint32_t move_bound;
+    uint32_t ring0;  // the bordered cell table's LDS address (step_group_ring)
     __device__ __forceinline__ U4 block(const Key& qk, uint32_t t, uint32_t slot) const {
         if constexpr (kSched) return draw_sched(ks, qk, t, slot);
         else return draw(qk, t, slot);
@@ -239,6 +242,157 @@ __device__ __forceinline__ bool step_group_state(const LdsWorld& w, const SeqInv
     return take_ran;
 }
 
+// The regular form of the state-only step, for a wave all of whose envs are regular: inside the
+// map and with a destination. No state-only step makes a regular env irregular (a select writes a
+// port's index, an arrival pick_other's result, and a move changes the position only to a cell
+// of the map), so the wave's one ballot where Carried is filled holds for the whole run. The
+// same next state as step_group_state, bit for bit, from less work per step:
+//   * U.pos is biased by one in both halves and the one cell lookup reads the bordered table
+//     (step_lean.h) at the move's target, always: the target's code says "off the map"
+//     (kRingBorder: the action is an error, no gate, no arrival), "ground" (a move that stays)
+//     or neither. No bounds test, no test for a destination, no select of the cell to read.
+//   * U.near: does any lane of the wave hold an env on a non-water cell (a ballot of the OR of
+//     the lane's four carried codes, taken after the move). It is this step's arrival vote, a
+//     conservative one (it also passes for a ship that stays on a port: the test inside is the
+//     position compare, as before), and the next step's first take vote: a take passes only on a
+//     port's cell, so the exact vote over the actions runs only behind it. take_ran stays the
+//     exact vote's result (the GATE pool's windows end on it).
+//   * the firing gates and the arrivals stay lane masks until a wave has one: the loss and
+//     arrival blocks build their bit words themselves.
+template <bool kNt, bool kSched, typename Late = NoLateDraw>
+__device__ __forceinline__ bool step_group_ring(const LdsWorld& w, const SeqInv<kSched>& I, const Key& qk, uint32_t t, U4 fb,
+                                                const U4& gb, Group<false, false, kNt>& G, Carried& U, Late late = Late{}) {
+    const int P = w.P;
+    const uint32_t wh = (uint32_t)(w.W + 2) | (1u << 16);
+    const uint32_t pm1 = P > 0 ? (uint32_t)(P - 1) : 0u;  // clamp for table reads whose value an error discards
+    bool take_ran = false;
+    if (U.near) {  // wave-uniform: some env of the wave is on a non-water cell
+        bool take_any = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) take_any |= (G.a[j] >= 4 + P) & (U.code[j] != 0);
+        take_ran = __builtin_amdgcn_ballot_w64(take_any) != 0;
+        if (take_ran) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int act = G.a[j];
+                const bool lt_tc = act < 54 + P;
+                const int amount = act - (lt_tc ? 4 + P : 54 + P);
+                const int2 st2 = U.take[U.code[j]];
+                const int stock = lt_tc ? st2.y : st2.x;
+                const bool ok_take = (act >= 4 + P) & (amount > 0) & (amount <= stock);
+                G.c[j] = (ok_take & lt_tc) ? G.c[j] + amount : G.c[j];
+                G.f[j] = (ok_take & !lt_tc) ? G.f[j] + (double)amount : G.f[j];
+                U.thr[j] = gate_thr_of(w, G.c[j]);
+            }
+        }
+    }
+    late(fb);
+    uint32_t np[4], code_t[4];
+    // MOVE: the four lookups at the targets first, in flight together
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        np[j] = pk_add_u16(U.pos[j], w.moves[G.a[j] & 3]);
+        code_t[j] = lds_cell(I.ring0, np[j], wh);
+    }
+    asm("" : "+v"(code_t[0]), "+v"(code_t[1]), "+v"(code_t[2]), "+v"(code_t[3]));
+    int dst[4], cg[4];
+    bool do_move[4], moved[4], fires[4];
+    double f[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int act = G.a[j];
+        const int val = (int)((uint32_t)act - 4u);
+        cg[j] = G.c[j];
+        const bool same = U.org[j] == val;
+        do_move[j] = ring_do_move(val, I.move_bound, code_t[j]);
+        moved[j] = ring_moved(val, I.move_bound, code_t[j]);
+        const bool sel_ok = lean_sel_ok(act, P, same);
+        U.pos[j] = moved[j] ? np[j] : U.pos[j];
+        U.code[j] = moved[j] ? code_t[j] : U.code[j];
+        dst[j] = sel_ok ? val : U.dst[j];
+        f[j] = lean_fuel(G.f[j], lean_fuel_scale(fb.v[j], kFifthPerWord), moved[j]);
+        fires[j] = do_move[j] & (cg[j] > 0) & (gb.v[j] <= U.thr[j]);
+    }
+    // the vote word: this step's arrival vote and the next step's first take vote
+    const bool near = __builtin_amdgcn_ballot_w64((U.code[0] | U.code[1] | U.code[2] | U.code[3]) != 0) != 0;
+    U.near = near;
+    uint32_t arrive = 0;
+    if (near) {
+        // (a mover selects nothing, so dst is still its dest); the port's position biased as the ship's is
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            arrive |= (uint32_t)(do_move[j] & (U.pos[j] == ring_bias(w.pos[min((uint32_t)dst[j], pm1)]))) << j;
+    }
+    int org[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        org[j] = U.org[j];
+        G.f[j] = f[j];
+    }
+    // cargo loss and arrival, only in waves with a firing gate / an arrival
+    if (__builtin_amdgcn_ballot_w64(fires[0] | fires[1] | fires[2] | fires[3]) != 0) {
+        uint32_t fire = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) fire |= (uint32_t)fires[j] << j;
+        asm volatile("" : "+v"(fire));
+        uint32_t lt[4], v1[4], v2[4], v3[4];
+        const uint32_t rk[4] = {0u, fire & 1u, (uint32_t)__popc(fire & 3u), (uint32_t)__popc(fire & 7u)};
+        U4 rr = I.block(qk, t, loss_slot(0));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            lt[j] = rr.v[0];
+            v1[j] = rr.v[1];
+            v2[j] = rr.v[2];
+            v3[j] = rr.v[3];
+        }
+#pragma unroll
+        for (uint32_t q = 1; q < 4; ++q) {
+            if (__popc(fire) > q) {
+                rr = I.block(qk, t, loss_slot(q));
+#pragma unroll
+                for (int j = (int)q; j < 4; ++j) {
+                    const bool take = rk[j] >= q;
+                    lt[j] = take ? rr.v[0] : lt[j];
+                    v1[j] = take ? rr.v[1] : v1[j];
+                    v2[j] = take ? rr.v[2] : v2[j];
+                    v3[j] = take ? rr.v[3] : v3[j];
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (__builtin_amdgcn_ballot_w64((fire >> j) & 1u) == 0) continue;
+            const uint32_t lo = min(v1[j], v2[j]), hi = max(v1[j], v2[j]);
+            const uint32_t med = max(lo, min(hi, v3[j]));  // v_med3_u32
+            const int part = beta_part(med, cg[j]);
+            const int some = lt[j] > kTypeHi ? cg[j] : part;
+            const int loss = lt[j] < kTypeLo ? 0 : some;
+            const bool fj = (fire >> j) & 1u;
+            cg[j] = fj ? cg[j] - loss : cg[j];
+            U.thr[j] = gate_thr_of(w, cg[j]);
+        }
+    }
+    if (arrive) {
+        const U4 ab = I.block(qk, t, kSlotArrive);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool aj = (arrive >> j) & 1u;
+            const int nd = pick_other(ab.v[j], P, dst[j]);
+            cg[j] = aj ? 0 : cg[j];
+            U.thr[j] = gate_thr_of(w, cg[j]);
+            org[j] = aj ? dst[j] : org[j];
+            dst[j] = aj ? nd : dst[j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        U.org[j] = org[j];
+        U.dst[j] = dst[j];
+        G.c[j] = cg[j];
+    }
+    return take_ran;
+}
+
 // The stocks by cell code for the state-only steps' take checks: 256 (fuel, cargo) pairs,
 // port i's at code i + 1 and zeros at every other code (0 water, kCellGround, codes past P),
 // so `0 < amount <= stock` is false wherever the ship is on no port. One entry per thread of
@@ -283,6 +437,7 @@ constexpr uint32_t kGatePoolRow = 64 + kGatePoolSeeds;  // uint4 entries per wav
 constexpr uint32_t kGateDirectRun = 16;   // steps of the direct draw between two votes
 constexpr uint32_t kGateEarlyCut = 2;     // a refilled window that a take ends within this many steps was cut early
 constexpr size_t kGatePoolBytes = (kStepBlock / 64) * kGatePoolRow * sizeof(uint4);  // 6 KiB
+constexpr int kRingRows = 3;  // (ring_r0 .. ring_r2) 16-byte units of the bordered cell table a thread loads ahead: 12 KiB, the 100 x 100 map's 10.2
 static_assert(kGatePoolLimit <= kGatePoolSeeds && kGatePoolLimit <= 32, "GATE pool: a window of at least 2 steps");
 
 // se_step_seq without auto-reset, fused: `steps` consecutive steps of the agent path in one
@@ -295,6 +450,11 @@ static_assert(kGatePoolLimit <= kGatePoolSeeds && kGatePoolLimit <= 32, "GATE po
 // step still moves is its 4 B action. Row k + 1 is loaded before step k's arithmetic, so its
 // latency (rows are read once, from HBM) hides behind the step. iters > 1: the group loop is
 // the outer one.
+// Behind the pools the launch stages the bordered cell table (step_lean.h), built by the host with
+// the world image and kept behind it in the world buffer (ring_bytes; 0: no table). A wave whose
+// envs are all regular steps with step_group_ring, in the pooled loop and in the direct run; a
+// wave with an irregular env, and every wave of a launch without the table, runs
+// step_group_state and draws directly for the whole run.
 // Only the last step's reward, done and err exist anywhere, so steps 0 .. steps - 2 run the
 // state-only step (step_group_state), with x | y, origin and dest unpacked once before them
 // and packed once after, and step steps - 1 alone runs the full one (step_group_agent<kKeep>).
@@ -312,9 +472,13 @@ __device__ __forceinline__ uint32_t seq_lane() {
 
 template <bool kNt, bool kPool>
 __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4))) void step_seq_kernel(
-    StepArgs A, int32_t steps, int64_t ld) {
+    StepArgs A, int32_t steps, int64_t ld, uint32_t ring_bytes) {
     extern __shared__ uint32_t lds[];
     if (steps <= 0) return;  // nothing to store (the host launches no empty run)
+    // The bordered cell table (step_lean.h) follows the image in the world buffer; ring_bytes == 0:
+    // this launch has none (launch-uniform), and every wave runs the general step.
+    const uint32_t ring16 = steps > 1 ? ring_bytes >> 4 : 0u;
+    const bool has_ring = ring16 != 0;
     const int64_t full = A.n >> 2;
     const int64_t first = (int64_t)blockIdx.x * A.iters * kStepBlock;  // block-uniform first group
 
@@ -327,26 +491,38 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
         const uint32_t lane = last < (int64_t)threadIdx.x ? (uint32_t)(last < 0 ? 0 : last) : threadIdx.x;
         G.template load<true>(A, At<true>{last < 0 ? full - 1 : first, 0, A.n}, lane);
     }
+    // the table's first kRingRows 16-byte units per thread, in flight behind the group's loads
+    // (the 100 x 100 map's are all of it). Clamped and unconditional, so they stay in registers (a
+    // launch without the table loads its first unit, which every world buffer has, and drops it)
+    const uint4* const ring_g = reinterpret_cast<const uint4*>(A.world + A.dims.padded());
+    const uint32_t ring_last = max(ring16, 1u) - 1u;
+    const uint4 ring_r0 = ring_g[min(threadIdx.x, ring_last)];
+    const uint4 ring_r1 = ring_g[min(threadIdx.x + kStepBlock, ring_last)];
+    const uint4 ring_r2 = ring_g[min(threadIdx.x + 2 * kStepBlock, ring_last)];
     __builtin_amdgcn_sched_barrier(0);
     const LdsWorld w = stage_finish(A.world, A.dims, lds, st);
     // the state-only steps' take checks: the stocks by cell code, behind the staged image
     int2* const take = reinterpret_cast<int2*>(lds + A.dims.padded());
     uint4* const gate_pool = reinterpret_cast<uint4*>(take + 256);  // kPool: behind the stock table
+    // the bordered cell table: behind the pools
+    uint4* const ring_l = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(take + 256) + (kPool ? kGatePoolBytes : 0));
     if (steps > 1) {  // launch-uniform
         stock_by_code(w, take);
+        if (has_ring) {
+            if (threadIdx.x < ring16) ring_l[threadIdx.x] = ring_r0;
+            if (threadIdx.x + kStepBlock < ring16) ring_l[threadIdx.x + kStepBlock] = ring_r1;
+            if (threadIdx.x + 2 * kStepBlock < ring16) ring_l[threadIdx.x + 2 * kStepBlock] = ring_r2;
+            for (uint32_t i = threadIdx.x + kStepBlock * kRingRows; i < ring16; i += kStepBlock) ring_l[i] = ring_g[i];  // larger maps
+        }
         __syncthreads();
     }
 
     // what the state-only steps read and no step changes: filled once per launch
     SeqInv<kPool> I;
     if (steps > 1) {
-        if constexpr (kPool) {
-            const Key sk = env_key(A.seed, 0);
-            I.ks = key_schedule(sk.k0, sk.k1);
-            pin_schedule(I.ks);
-        }
         I.move_bound = lean_move_bound(w.P);
         asm volatile("" : "+s"(I.move_bound));
+        I.ring0 = lds_address(reinterpret_cast<const uint8_t*>(ring_l));
     }
 
     BlockStats bs;
@@ -361,7 +537,6 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
             asm volatile("" : "+v"(lane));
             G.template load<true>(A, At<true>{g0, 0, A.n}, lane);
         }
-        const At<true> at0{g0, g * 4, A.n};
         const uint32_t tl = A.t + (uint32_t)(steps - 1);  // the last step's counter
         if (steps > 1) {
             // steps 0 .. steps - 2, state only: x | y, origin and dest one register per env
@@ -375,26 +550,62 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                 U.thr[j] = gate_thr_of(w, G.c[j]);
             }
             U.take = take;
+            // The wave's path for the run: the regular step on the bordered table where the launch
+            // has one and every env of the wave is inside the map with a destination (no state-only
+            // step undoes either, step_group_ring), the general step drawing directly otherwise.
+            bool irregular = false;
+            {
+                const uint32_t lim = (uint32_t)(w.H - 1) | ((uint32_t)(w.W - 1) << 16);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) irregular |= (U.dst[j] == SE_NONE) | (pk_min_u16(U.pos[j], lim) != U.pos[j]);
+            }
+            const bool ring = has_ring && __builtin_amdgcn_ballot_w64(irregular) == 0;  // wave-uniform
+            U.near = __builtin_amdgcn_ballot_w64((U.code[0] | U.code[1] | U.code[2] | U.code[3]) != 0) != 0;
+            if (ring) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) U.pos[j] = ring_bias(U.pos[j]);
+            }
             // the step-invariant parts of the quad's FUEL and GATE blocks (philox.h, draw2),
             // opaque so the loop keeps them in registers as computed here
             const Key qk = env_key(A.seed, (A.env_base + g * 4) >> 2);
             PairInv inv = pair_invariants(qk);
             asm volatile("" : "+v"(inv.hi[0]), "+v"(inv.lo[0]), "+v"(inv.hi[1]), "+v"(inv.lo[1]));
             const int32_t* row = A.act;
-            if constexpr (!kPool) {
+            if (!ring) {
+                // no key schedule here (the rare draws are draw()'s): a third copy of the step with
+                // the schedule's 20 registers live beside it does not fit under 128
+                SeqInv<false> Ig;
+                Ig.move_bound = I.move_bound;
+                const uint32_t lane = seq_lane<kPool>();
                 for (uint32_t t = A.t; t != tl; ++t) {
                     // the next row's actions (there is one: the last step follows)
                     row += ld;
                     int32_t nxt[4];
+                    ld4_full<kNt>(row, g0, nxt, lane);
+                    const U4x2 fg = draw2(qk, inv, t);
+                    step_group_state(w, Ig, qk, t, fg.fuel, fg.gate, G, U);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
+                }
+            } else if constexpr (!kPool) {
+                for (uint32_t t = A.t; t != tl; ++t) {
+                    row += ld;
+                    int32_t nxt[4];
                     ld4_full<kNt>(row, g0, nxt);
                     const U4x2 fg = draw2(qk, inv, t);
-                    step_group_state(w, I, qk, t, fg.fuel, fg.gate, G, U);
+                    step_group_ring(w, I, qk, t, fg.fuel, fg.gate, G, U);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
                 }
             } else {
                 // the wave's GATE pool (above): vote, then a window from the pool or a few
-                // steps of the direct draw, until the run's inner steps are done
+                // steps of the direct draw, until the run's inner steps are done. The key schedule
+                // is filled here, per group, so that it is live in the regular waves' loops alone.
+                {
+                    const Key sk = env_key(A.seed, 0);
+                    I.ks = key_schedule(sk.k0, sk.k1);
+                    pin_schedule(I.ks);
+                }
                 const uint32_t lane = seq_lane<true>(), L = lane & 63u;
                 uint4* const pool = gate_pool + (lane >> 6) * kGatePoolRow;
                 uint4* const seeds = pool + 64;
@@ -403,68 +614,65 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                 const bool whole = __builtin_amdgcn_ballot_w64(true) == ~0ull;
                 uint32_t cuts = 0;  // refilled windows in a row that a take cut early
                 for (uint32_t t = A.t; t != tl;) {
-                    // The pooled steps, window after window in one loop: the vote and the refill
-                    // are a block inside it, so the state stays in its registers from window to
-                    // window, and only a wave that leaves for the direct draw moves it.
-                    uint32_t win = 0, s = 0, wmask = 0;  // steps left in the window, its offset, W - 1
-                    const uint4* mine = pool;
-                    bool pooled = true, drew = false;
+                    // The pooled steps, window after window in one loop, so the state stays in its
+                    // registers from window to window, and only a wave that leaves for the direct
+                    // draw moves it: a few steps of it, and the wave votes again.
+                    bool pooled = true;
                     do {
-                        if (win == 0) {
-                            const bool carry = (G.c[0] > 0) | (G.c[1] > 0) | (G.c[2] > 0) | (G.c[3] > 0);
-                            const uint64_t M = __builtin_amdgcn_ballot_w64(carry);
-                            const uint32_t m = (uint32_t)__popcll(M);
-                            if (!whole || m > kGatePoolLimit || (cuts >= 2 && m != 0)) {
-                                pooled = false;
-                                break;
-                            }
-                            drew = m != 0;
-                            // the window: the largest power of two W <= 8 with m W <= 64
-                            const uint32_t logw = gate_window_log2(m);
-                            const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
-                            wmask = (1u << logw) - 1u;
-                            if (m != 0) {
-                                if (carry) seeds[slot] = make_uint4(inv.c3, inv.hi[1], inv.lo[1], qk.e1);
-                                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                                __builtin_amdgcn_wave_barrier();
-                                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                                // lane L draws carrier L >> logw's block at window offset L & (W - 1);
-                                // past the last carrier: the last one's again, which nobody's gate reads
-                                const uint4 sd = seeds[min(L >> logw, m - 1u)];
-                                const U4 gw = draw_gate_pooled_sched(I.ks, GateSeed{sd.x, sd.y, sd.z, sd.w}, t + (L & wmask));
-                                pool[L] = make_uint4(gw.v[0], gw.v[1], gw.v[2], gw.v[3]);
-                                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                                __builtin_amdgcn_wave_barrier();
-                                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                            }
-                            // a carrier's words for offset s are entry slot W + s < 64. Another lane's
-                            // slot is at most m: it reads some entry below 64 + W (the seeds follow
-                            // the pool), whose words its gate never tests. m == 0: no entry holds
-                            // anything, no gate tests a word, and the window lasts until a take ends it.
-                            mine = pool + ((slot << logw) & 63u);
-                            win = m != 0 ? min(tl - t, wmask + 1u) : tl - t;  // t may wrap 2^32 inside the run
-                            s = 0;
+                        // the vote
+                        const bool carry = (G.c[0] > 0) | (G.c[1] > 0) | (G.c[2] > 0) | (G.c[3] > 0);
+                        const uint64_t M = __builtin_amdgcn_ballot_w64(carry);
+                        const uint32_t m = (uint32_t)__popcll(M);
+                        if (!whole || m > kGatePoolLimit || (cuts >= 2 && m != 0)) {
+                            pooled = false;
+                            break;
                         }
-                        row += ld;
-                        int32_t nxt[4];
-                        ld4_full<kNt>(row, g0, nxt, lane);
-                        const uint4 g4 = mine[s & wmask];
-                        // FUEL alone, drawn after the take block (step_group_state's `late`)
-                        const auto fuel = [&](U4& fb) {
-                            fb = draw_fuel_sched(I.ks, qk, inv, t);
-                            asm volatile("" : "+v"(fb.v[0]), "+v"(fb.v[1]), "+v"(fb.v[2]), "+v"(fb.v[3]));
-                        };
-                        const bool took = step_group_state(w, I, qk, t, U4{}, U4{{g4.x, g4.y, g4.z, g4.w}}, G, U, fuel);
+                        // the window: the largest power of two W <= 8 with m W <= 64
+                        const uint32_t logw = gate_window_log2(m);
+                        const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
+                        const uint32_t wmask = (1u << logw) - 1u;
+                        if (m != 0) {
+                            if (carry) seeds[slot] = make_uint4(inv.c3, inv.hi[1], inv.lo[1], qk.e1);
+                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                            __builtin_amdgcn_wave_barrier();
+                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                            // lane L draws carrier L >> logw's block at window offset L & (W - 1);
+                            // past the last carrier: the last one's again, which nobody's gate reads
+                            const uint4 sd = seeds[min(L >> logw, m - 1u)];
+                            const U4 gw = draw_gate_pooled_sched(I.ks, GateSeed{sd.x, sd.y, sd.z, sd.w}, t + (L & wmask));
+                            pool[L] = make_uint4(gw.v[0], gw.v[1], gw.v[2], gw.v[3]);
+                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                            __builtin_amdgcn_wave_barrier();
+                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        }
+                        // a carrier's words for offset s are entry slot W + s < 64. Another lane's
+                        // slot is at most m: it reads some entry below 64 + W (the seeds follow
+                        // the pool), whose words its gate never tests. m == 0: no entry holds
+                        // anything, no gate tests a word, and the window lasts until a take ends it.
+                        const uint4* const mine = pool + ((slot << logw) & 63u);
+                        const uint32_t win = m != 0 ? min(tl - t, wmask + 1u) : tl - t;  // t may wrap 2^32 inside the run
+                        // The window's steps, a counted loop that a take leaves early: a take may have
+                        // made a carrier, so the wave votes again (wave-uniform).
+                        uint32_t s = 0;
+                        bool took;
+                        do {
+                            row += ld;
+                            int32_t nxt[4];
+                            ld4_full<kNt>(row, g0, nxt, lane);
+                            const uint4 g4 = mine[s & wmask];
+                            // FUEL alone, drawn after the take block (the step's `late`)
+                            const auto fuel = [&](U4& fb) {
+                                fb = draw_fuel_sched(I.ks, qk, inv, t);
+                                asm volatile("" : "+v"(fb.v[0]), "+v"(fb.v[1]), "+v"(fb.v[2]), "+v"(fb.v[3]));
+                            };
+                            took = step_group_ring(w, I, qk, t, U4{}, U4{{g4.x, g4.y, g4.z, g4.w}}, G, U, fuel);
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
-                        ++s;
-                        ++t;
-                        if (took) {  // a take may have made a carrier: vote again (wave-uniform)
-                            cuts = drew && s <= kGateEarlyCut ? cuts + 1u : 0u;
-                            win = 0;
-                        } else if (--win == 0) {
-                            cuts = 0;
-                        }
+                            for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
+                            ++s;
+                            ++t;
+                        } while (!took && s != win);
+                        // refilled windows in a row that a take cut early
+                        cuts = took && m != 0 && s <= kGateEarlyCut ? cuts + 1u : 0u;
                     } while (t != tl);
                     if (pooled) break;
                     cuts = min(cuts, 1u);
@@ -473,11 +681,15 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                         int32_t nxt[4];
                         ld4_full<kNt>(row, g0, nxt, lane);
                         const U4x2 fg = draw2(qk, inv, t);
-                        step_group_state(w, I, qk, t, fg.fuel, fg.gate, G, U);
+                        step_group_ring(w, I, qk, t, fg.fuel, fg.gate, G, U);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
                     }
                 }
+            }
+            if (ring) {  // the bias comes off once
+#pragma unroll
+                for (int j = 0; j < 4; ++j) U.pos[j] = ring_unbias(U.pos[j]);
             }
             // back into the Group's packed bytes
             pack_pos(U.pos, G.x, G.y);
@@ -490,9 +702,9 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
         }
         // the last step in full: its reward, done and err are the run's
         StepOut O;
-        const uint32_t ln = seq_lane<kPool>();
-        const At<true> at = kPool ? At<true>{g0, (g0 + ln) * 4, A.n} : at0;
-        step_group_agent<false, true, kNt, false, false, true>(A, w, G, at, bs, F, early_draws<false>(A, kPool ? at.base : g * 4, tl), tl, &O);
+        const uint32_t ln = seq_lane<true>();
+        const At<true> at{g0, (g0 + ln) * 4, A.n};
+        step_group_agent<false, true, kNt, false, false, true>(A, w, G, at, bs, F, early_draws<false>(A, at.base, tl), tl, &O);
         const se_state& S = late_args().st;
         __builtin_amdgcn_sched_barrier(0);  // the fuel halves back to back (store_moved)
         st4u8_full(S.x, g0, G.x, ln);
