@@ -258,12 +258,19 @@ static int move_ship(const orc_world* w, ship* s, int64_t mx, int64_t my, source
     /* :318-323: loss gate normalize(cargo, 50, 0) = cargo / 50 (util.py:6-8) */
     double likelihood = (double)s->cargo / (double)MAX_CARGO_CAPACITY;
     const int production = !src->tape && !src->roll;
-    if (u_gate <= likelihood && !(production && s->cargo == 0)) {
+    /* A staged replay (a variate missing from the tape, answered with E_NEED_DRAW) names in `used`
+     * only the draws the step is known to make on what the tape holds: from cargo 50 on the gate
+     * fires whatever it draws (random() < 1 <= cargo / 50), so a missing u_gate still reports the
+     * loss type; a missing loss type does not decide between no, partial and total loss, so it
+     * reports no beta. With every variate present neither changes anything. */
+    const int fires = u_gate <= likelihood || (src->tape && s->cargo >= MAX_CARGO_CAPACITY);
+    if (fires && !(production && s->cargo == 0)) {
         /* _calculate_cargo_loss :169-200: the loss-type draw happens first, always
          * (production skips cargo 0, which loses nothing whatever the draw) */
         double lt = src_loss_type(src);
         int32_t loss;
         if (s->cargo == 0) loss = 0;
+        else if (src->tape && isnan(lt)) loss = 0;
         else if (lt < 0.1) loss = 0;
         else if (lt > 0.9) loss = s->cargo;
         else loss = (int32_t)(src_beta(src) * (double)s->cargo); /* int() truncation */
