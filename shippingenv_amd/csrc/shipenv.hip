@@ -115,6 +115,7 @@ struct se_env {
     int32_t seq_max_steps = 1024;  // steps of one fused launch at most (seq_max_steps)
     bool seq_gate_pool = true;  // the fused launch draws GATE through the wave's pool (SHIPENV_SEQ_GATE_POOL=0: draw2)
     bool seq_ring = true;       // the fused launch's regular waves step on the bordered cell table (SHIPENV_SEQ_RING=0: none do)
+    bool seq_screen = true;     // the GATE pool's refill screens its words, cold steps test no gate (SHIPENV_SEQ_SCREEN=0: every step does)
 };
 
 // A host-resident world (se_host_*): no device, no HIP call. It steps envs whose SoA
@@ -130,9 +131,9 @@ namespace {
 #include "host.h"  // fail, HIP_TRY, DeviceGuard, device blocks, the LDS opt-in, check_ready
 
 // ---------------------------------------------------------------- launch-time switches
-// SHIPENV_STEP_BLOCKS, _DONE_PAD, _NT_LOADS, _SEQ_MAX_STEPS, _SEQ_FUSE, _SEQ_GATE_POOL, _SEQ_RING
-// and _MASK_TILED: se_create resolves all eight, once, into the se_env, and a launch reads no
-// environment variable.
+// SHIPENV_STEP_BLOCKS, _DONE_PAD, _NT_LOADS, _SEQ_MAX_STEPS, _SEQ_FUSE, _SEQ_GATE_POOL, _SEQ_RING,
+// _SEQ_SCREEN and _MASK_TILED: se_create resolves all nine, once, into the se_env, and a launch
+// reads no environment variable.
 
 // Workgroup cap of the step kernel: each thread then walks ceil(groups / (cap*256))
 // groups, loading the next group after storing the current one.
@@ -203,6 +204,15 @@ bool seq_ring() {
     return !v || atoi(v) != 0;
 }
 
+// SHIPENV_SEQ_SCREEN=0: every step of a pooled window counts as hot (the launch's screen_all is
+// all-ones, OR-ed into each window's screen), so every step reads its pool entry and tests the
+// gate, as before the screen (step_seq.h): the same-library control of the screen's measurements
+// and tests. Results are the same bits either way.
+bool seq_screen() {
+    const char* v = getenv("SHIPENV_SEQ_SCREEN");
+    return !v || atoi(v) != 0;
+}
+
 // SHIPENV_MASK_TILED=1: se_valid_mask takes the round-4 tiled kernel (valid_mask_tiled_kernel)
 // where it would take the row templates; tests reach that kernel at small P this way.
 bool mask_tiled() {
@@ -238,9 +248,9 @@ int build_world_image(int H, int W, const std::vector<uint8_t>& water, int32_t P
     for (int c = 0; c < 50; ++c) {
         const double q = (double)c / kMaxCargo;
         memcpy(&img[d.frac() + 2 * c], &q, sizeof q);
-        img[d.gate() + c] = (uint32_t)floor(ldexp(q, 32));  // exact product, q < 1
     }
-    img[d.gate() + 50] = 0xffffffffu;  // cargo >= 50: random() < 1 <= cargo / 50
+    // exact product, q < 1; cargo >= 50: random() < 1 <= cargo / 50 (step_lean.h)
+    for (int c = 0; c <= 50; ++c) img[d.gate() + c] = gate_thr_entry(c, kMaxCargo);
     // N, E, S, W as packed 16-bit (dx, dy) (shipping/type.py:8-16)
     const int mdx[4] = {0, -1, 0, 1}, mdy[4] = {-1, 0, 1, 0};
     for (int k = 0; k < 4; ++k)
@@ -422,7 +432,7 @@ int launch_step_seq(se_env* env, const int32_t* act, int64_t ld, int32_t steps, 
         const size_t lds = without + ring;
         const auto kernel = pool ? (env->nt_loads ? step_seq_kernel<true, true> : step_seq_kernel<false, true>)
                                  : (env->nt_loads ? step_seq_kernel<true, false> : step_seq_kernel<false, false>);
-        kernel<<<env->grid, kStepBlock, lds, s>>>(A, steps, ld, ring);
+        kernel<<<env->grid, kStepBlock, lds, s>>>(A, steps, ld, ring, env->seq_screen ? 0u : ~0u);
         HIP_TRY(hipGetLastError());
     }
     if (env->n & 3) {
@@ -510,6 +520,7 @@ int se_create(se_env** out, int device, int64_t n, int64_t env_id_base, int32_t 
         env->seq_max_steps = seq_max_steps();
         env->seq_gate_pool = seq_gate_pool();
         env->seq_ring = seq_ring();
+        env->seq_screen = seq_screen();
         env->mask_tiled = mask_tiled();
     }
     hipError_t e = hipMalloc(&env->d_slab, (size_t)env->nslab * 4 * sizeof(double));

@@ -2,10 +2,11 @@
 // step_group_state), as host + device helpers: tools/step_lean_check.cpp compares them on the
 // host with the forms they replaced (the error cascade's terms, the select of -scale / -0.0),
 // tools/step_trim_check.cpp the move test on val, the fuel scale's FMA and the GATE pool's
-// window choice, and tools/step_ring_check.cpp the regular step's decode on the bordered cell
-// table with the general form's.
+// window choice, tools/step_ring_check.cpp the regular step's decode on the bordered cell
+// table with the general form's, and tools/step_screen_check.cpp the GATE pool's screen.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 namespace shipenv {
@@ -109,6 +110,37 @@ __host__ __device__ __forceinline__ double lean_fuel_scale(uint32_t w, double fi
 // m <= 16; beyond 16 carriers (where the kernel draws directly) 2.
 __host__ __device__ __forceinline__ uint32_t gate_window_log2(uint32_t m) {
     return m <= 8 ? 3u : m <= 16 ? 2u : 1u;
+}
+
+// Entry c of the world image's gate thresholds: the gate of a ship with cargo c fires for a word
+// <= floor(c / max_cargo * 2^32) (random() < cargo / 50, the quotient correctly rounded and the
+// product exact), and for every word from max_cargo on. Entry 0 is 0 and the entries never fall
+// as c rises, which the screen below rests on.
+__host__ __forceinline__ uint32_t gate_thr_entry(int c, double max_cargo) {
+    return c < (int)max_cargo ? (uint32_t)floor(ldexp((double)c / max_cargo, 32)) : 0xffffffffu;
+}
+
+// The screened GATE pool (step_seq.h). At a refill the lane that drew a carrier's block for one
+// window offset compares its four words with that carrier's four thresholds as they stood at the
+// vote: screen_hot. Inside a window cargo only falls (a loss or an arrival lowers it; a take ends
+// the window, and its env did not move in that step), the thresholds never rise as cargo falls,
+// and an env without cargo has threshold 0 and fires for no word. So a gate can fire at an offset
+// only if the screen passed there: a word above its threshold at the refill stays above it.
+// (A word equal to 0 passes for an env without cargo, for nothing: the screen is only wider.)
+__host__ __device__ __forceinline__ bool screen_hot(const uint32_t word[4], const uint32_t thr[4]) {
+    return (word[0] <= thr[0]) | (word[1] <= thr[1]) | (word[2] <= thr[2]) | (word[3] <= thr[3]);
+}
+// The ballot of screen_hot over the wave's 64 lanes, lane L = carrier L >> logw at offset
+// L & (W - 1), W = 1 << logw, folded to one bit per window offset: the OR of the ballot's groups
+// of W lanes, in bits 0 .. W - 1. The bits from W up hold partial ORs that nobody reads (a window's
+// steps test bits 0 .. W - 1 only), so the kernel masks nothing. logw is gate_window_log2's, 1 .. 3.
+__host__ __device__ __forceinline__ uint32_t screen_fold(uint64_t ballot, uint32_t logw) {
+    uint32_t b = (uint32_t)ballot | (uint32_t)(ballot >> 32);
+    b |= b >> 16;
+    b |= b >> 8;
+    b |= logw < 3u ? b >> 4 : 0u;
+    b |= logw < 2u ? b >> 2 : 0u;
+    return b;
 }
 
 }  // namespace shipenv

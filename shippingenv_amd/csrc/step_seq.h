@@ -259,9 +259,36 @@ __device__ __forceinline__ bool step_group_state(const LdsWorld& w, const SeqInv
 //     exact vote's result (the GATE pool's windows end on it).
 //   * the firing gates and the arrivals stay lane masks until a wave has one: the loss and
 //     arrival blocks build their bit words themselves.
-template <bool kNt, bool kSched, typename Late = NoLateDraw>
+//   * the GATE words come from `gate`. GateDrawn: the caller drew them, and the step tests them.
+//     GateScreened (the pooled window, below): the refill has screened the window's words, and on a
+//     cold step (hot false, wave-uniform), where no gate of the wave can fire, the step reads no
+//     word, tests no gate and has no loss block; do_move is then made only behind `near`, where
+//     the arrival test reads it.
+struct GateDrawn {
+    static constexpr bool kScreened = false;
+    const U4& gb;
+    __device__ __forceinline__ bool hot() const { return true; }
+    __device__ __forceinline__ U4 words() const { return gb; }
+};
+// A value as the branch it is read in sees it: the two places where a screened step makes do_move
+// (behind `near`, on a hot step) each compare their own copy, so the compares stay inside their
+// branches; written on the plain value they were hoisted into the step's main block, where a cold
+// step away from the ports paid for them.
+__device__ __forceinline__ uint32_t here(uint32_t v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+template <typename Read>
+struct GateScreened {
+    static constexpr bool kScreened = true;
+    bool is_hot;
+    Read read;  // the lane's pool entry for this step
+    __device__ __forceinline__ bool hot() const { return is_hot; }
+    __device__ __forceinline__ U4 words() const { return read(); }
+};
+template <bool kNt, bool kSched, typename Gate, typename Late = NoLateDraw>
 __device__ __forceinline__ bool step_group_ring(const LdsWorld& w, const SeqInv<kSched>& I, const Key& qk, uint32_t t, U4 fb,
-                                                const U4& gb, Group<false, false, kNt>& G, Carried& U, Late late = Late{}) {
+                                                const Gate& gate, Group<false, false, kNt>& G, Carried& U, Late late = Late{}) {
     const int P = w.P;
     const uint32_t wh = (uint32_t)(w.W + 2) | (1u << 16);
     const uint32_t pm1 = P > 0 ? (uint32_t)(P - 1) : 0u;  // clamp for table reads whose value an error discards
@@ -304,14 +331,14 @@ __device__ __forceinline__ bool step_group_ring(const LdsWorld& w, const SeqInv<
         const int val = (int)((uint32_t)act - 4u);
         cg[j] = G.c[j];
         const bool same = U.org[j] == val;
-        do_move[j] = ring_do_move(val, I.move_bound, code_t[j]);
+        if constexpr (!Gate::kScreened) do_move[j] = ring_do_move(val, I.move_bound, code_t[j]);
         moved[j] = ring_moved(val, I.move_bound, code_t[j]);
         const bool sel_ok = lean_sel_ok(act, P, same);
         U.pos[j] = moved[j] ? np[j] : U.pos[j];
         U.code[j] = moved[j] ? code_t[j] : U.code[j];
         dst[j] = sel_ok ? val : U.dst[j];
         f[j] = lean_fuel(G.f[j], lean_fuel_scale(fb.v[j], kFifthPerWord), moved[j]);
-        fires[j] = do_move[j] & (cg[j] > 0) & (gb.v[j] <= U.thr[j]);
+        if constexpr (!Gate::kScreened) fires[j] = do_move[j] & (cg[j] > 0) & (gate.words().v[j] <= U.thr[j]);
     }
     // the vote word: this step's arrival vote and the next step's first take vote
     const bool near = __builtin_amdgcn_ballot_w64((U.code[0] | U.code[1] | U.code[2] | U.code[3]) != 0) != 0;
@@ -320,8 +347,10 @@ __device__ __forceinline__ bool step_group_ring(const LdsWorld& w, const SeqInv<
     if (near) {
         // (a mover selects nothing, so dst is still its dest); the port's position biased as the ship's is
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < 4; ++j) {
+            if constexpr (Gate::kScreened) do_move[j] = ring_do_move((int)((uint32_t)G.a[j] - 4u), I.move_bound, here(code_t[j]));
             arrive |= (uint32_t)(do_move[j] & (U.pos[j] == ring_bias(w.pos[min((uint32_t)dst[j], pm1)]))) << j;
+        }
     }
     int org[4];
 #pragma unroll
@@ -330,7 +359,19 @@ __device__ __forceinline__ bool step_group_ring(const LdsWorld& w, const SeqInv<
         G.f[j] = f[j];
     }
     // cargo loss and arrival, only in waves with a firing gate / an arrival
-    if (__builtin_amdgcn_ballot_w64(fires[0] | fires[1] | fires[2] | fires[3]) != 0) {
+    bool any_fire = false;  // wave-uniform
+    if constexpr (Gate::kScreened) {
+        if (gate.hot()) {  // wave-uniform: the refill's screen passed for this step
+            const U4 gb = gate.words();
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                fires[j] = ring_do_move((int)((uint32_t)G.a[j] - 4u), I.move_bound, here(code_t[j])) & (cg[j] > 0) & (gb.v[j] <= U.thr[j]);
+            any_fire = __builtin_amdgcn_ballot_w64(fires[0] | fires[1] | fires[2] | fires[3]) != 0;
+        }
+    } else {
+        any_fire = __builtin_amdgcn_ballot_w64(fires[0] | fires[1] | fires[2] | fires[3]) != 0;
+    }
+    if (any_fire) {
         uint32_t fire = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) fire |= (uint32_t)fires[j] << j;
@@ -431,6 +472,19 @@ __device__ __forceinline__ void stock_by_code(const LdsWorld& w, int2* take) {
 // read) and with the group. The rows are wave-private and one wave's LDS operations execute in
 // order, so there is no __syncthreads: wavefront-scope fences and wave barriers keep the
 // compiler's order. Per wave 64 pool entries and kGatePoolSeeds seed rows of 16 B.
+// The screen. The words of a window are known at its refill, up to 8 steps before they are tested,
+// and so are the thresholds they can meet: inside a window cargo only falls, and gate_thr never
+// rises as cargo falls (step_lean.h, screen_hot). So each carrier also writes its four carried
+// thresholds to seed row kGatePoolLimit + rank (rows the limit of 16 leaves unused), the lane
+// that drew a block compares its words with that row, and the ballot, folded in scalar code to
+// one bit per window offset (screen_fold), says on which steps of the window a gate of the wave
+// can fire at all. A step whose bit is clear is cold: it reads no pool entry, tests no gate, has
+// no loss branch, and makes do_move only behind `near` (step_group_ring, GateScreened). In the
+// flagship run about 84 % of the wave-steps are cold (profiles/seq_screen/freq.json). A
+// window still ends where it did: a take by a lane that carries raises that lane's threshold,
+// and the screen would be stale. m == 0: the screen is 0. The launch's screen_all
+// (SHIPENV_SEQ_SCREEN=0: all-ones) is OR-ed into every window's screen: every step hot, the loop
+// before the screen. The direct runs test every gate.
 constexpr uint32_t kGatePoolLimit = 16;   // carrier lanes up to which a wave pools (W >= 4)
 constexpr uint32_t kGatePoolSeeds = 32;   // seed rows per wave: room for a limit of 32 (W = 2)
 constexpr uint32_t kGatePoolRow = 64 + kGatePoolSeeds;  // uint4 entries per wave
@@ -439,6 +493,7 @@ constexpr uint32_t kGateEarlyCut = 2;     // a refilled window that a take ends 
 constexpr size_t kGatePoolBytes = (kStepBlock / 64) * kGatePoolRow * sizeof(uint4);  // 6 KiB
 constexpr int kRingRows = 3;  // (ring_r0 .. ring_r2) 16-byte units of the bordered cell table a thread loads ahead: 12 KiB, the 100 x 100 map's 10.2
 static_assert(kGatePoolLimit <= kGatePoolSeeds && kGatePoolLimit <= 32, "GATE pool: a window of at least 2 steps");
+static_assert(2 * kGatePoolLimit <= kGatePoolSeeds, "GATE pool: the carriers' threshold rows follow their seed rows");
 
 // se_step_seq without auto-reset, fused: `steps` consecutive steps of the agent path in one
 // launch, on step_kernel's grid and ownership. Nothing outside the stream can observe the
@@ -472,7 +527,7 @@ __device__ __forceinline__ uint32_t seq_lane() {
 
 template <bool kNt, bool kPool>
 __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4))) void step_seq_kernel(
-    StepArgs A, int32_t steps, int64_t ld, uint32_t ring_bytes) {
+    StepArgs A, int32_t steps, int64_t ld, uint32_t ring_bytes, uint32_t screen_all) {
     extern __shared__ uint32_t lds[];
     if (steps <= 0) return;  // nothing to store (the host launches no empty run)
     // The bordered cell table (step_lean.h) follows the image in the world buffer; ring_bytes == 0:
@@ -593,7 +648,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                     int32_t nxt[4];
                     ld4_full<kNt>(row, g0, nxt);
                     const U4x2 fg = draw2(qk, inv, t);
-                    step_group_ring(w, I, qk, t, fg.fuel, fg.gate, G, U);
+                    step_group_ring(w, I, qk, t, fg.fuel, GateDrawn{fg.gate}, G, U);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
                 }
@@ -631,16 +686,31 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                         const uint32_t logw = gate_window_log2(m);
                         const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
                         const uint32_t wmask = (1u << logw) - 1u;
+                        // the window's screen, one bit per offset (step_lean.h): can a gate fire there?
+                        // m == 0: no, however long the window (0 or all-ones: any bit of it will do).
+                        // screen_all (SHIPENV_SEQ_SCREEN=0): every step is hot.
+                        uint32_t screen = screen_all;
                         if (m != 0) {
-                            if (carry) seeds[slot] = make_uint4(inv.c3, inv.hi[1], inv.lo[1], qk.e1);
+                            if (carry) {
+                                seeds[slot] = make_uint4(inv.c3, inv.hi[1], inv.lo[1], qk.e1);
+                                // the thresholds at the vote (0 for an env without cargo: gate_thr's entry 0)
+                                seeds[kGatePoolLimit + slot] = make_uint4(U.thr[0], U.thr[1], U.thr[2], U.thr[3]);
+                            }
                             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                             __builtin_amdgcn_wave_barrier();
                             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                             // lane L draws carrier L >> logw's block at window offset L & (W - 1);
                             // past the last carrier: the last one's again, which nobody's gate reads
-                            const uint4 sd = seeds[min(L >> logw, m - 1u)];
+                            const uint32_t of = min(L >> logw, m - 1u);
+                            const uint4 sd = seeds[of];
+                            const uint4 th = seeds[kGatePoolLimit + of];
                             const U4 gw = draw_gate_pooled_sched(I.ks, GateSeed{sd.x, sd.y, sd.z, sd.w}, t + (L & wmask));
                             pool[L] = make_uint4(gw.v[0], gw.v[1], gw.v[2], gw.v[3]);
+                            // screen_hot (step_lean.h) word by word: four compares into lane masks, OR-ed in
+                            // scalar code (as one bool expression it compiled to 15 VALU of selects and shifts)
+                            const uint64_t hot = __builtin_amdgcn_ballot_w64(gw.v[0] <= th.x) | __builtin_amdgcn_ballot_w64(gw.v[1] <= th.y) |
+                                                 __builtin_amdgcn_ballot_w64(gw.v[2] <= th.z) | __builtin_amdgcn_ballot_w64(gw.v[3] <= th.w);
+                            screen |= screen_fold(hot, logw);
                             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                             __builtin_amdgcn_wave_barrier();
                             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -659,13 +729,17 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                             row += ld;
                             int32_t nxt[4];
                             ld4_full<kNt>(row, g0, nxt, lane);
-                            const uint4 g4 = mine[s & wmask];
+                            // the lane's words, read on a hot step only
+                            const auto words = [&]() {
+                                const uint4 g4 = mine[s & wmask];
+                                return U4{{g4.x, g4.y, g4.z, g4.w}};
+                            };
                             // FUEL alone, drawn after the take block (the step's `late`)
                             const auto fuel = [&](U4& fb) {
                                 fb = draw_fuel_sched(I.ks, qk, inv, t);
                                 asm volatile("" : "+v"(fb.v[0]), "+v"(fb.v[1]), "+v"(fb.v[2]), "+v"(fb.v[3]));
                             };
-                            took = step_group_ring(w, I, qk, t, U4{}, U4{{g4.x, g4.y, g4.z, g4.w}}, G, U, fuel);
+                            took = step_group_ring(w, I, qk, t, U4{}, GateScreened<decltype(words)>{((screen >> (s & 31u)) & 1u) != 0, words}, G, U, fuel);
 #pragma unroll
                             for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
                             ++s;
@@ -681,7 +755,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                         int32_t nxt[4];
                         ld4_full<kNt>(row, g0, nxt, lane);
                         const U4x2 fg = draw2(qk, inv, t);
-                        step_group_ring(w, I, qk, t, fg.fuel, fg.gate, G, U);
+                        step_group_ring(w, I, qk, t, fg.fuel, GateDrawn{fg.gate}, G, U);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
                     }
