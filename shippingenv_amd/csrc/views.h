@@ -436,6 +436,8 @@ __global__ __launch_bounds__(kBlock) void valid_mask_tmpl_kernel(MaskArgs A, con
                 }
             }
             desc[threadIdx.x] = id * (uint32_t)TB;
+            // read only for row 255 of a full tile, whose last chunk ends on the tile's end (256 * S is a
+            // multiple of 16), so nx is -16 and the window is a block's zero prefix: any block start serves
             if (threadIdx.x == 0) desc[kTileRows] = 0;
         }
         __syncthreads();
