@@ -79,6 +79,9 @@ typedef struct se_done_rec {
 
 /* Per-env SoA state, one entry per environment, all device pointers (16-B aligned).
  * ep_return, ep_start, done_recs and done_count may be NULL unless SE_FLAG_AUTO_RESET.
+ * Without that flag a step never writes them, bound or not; se_reset / se_reset_to write
+ * ep_return and ep_start of the envs they reset whenever they are bound. No call writes outside
+ * the documented entries of a buffer, before its first or past its last.
  * All calls on one env must be ordered on one stream (or externally synchronised):
  * the step kernel updates each wave's statistics-slab entry and the done lists with
  * plain loads and stores, which assumes no other launch on the same env overlaps it. */
@@ -108,12 +111,16 @@ typedef struct se_state {
                            checkpoint restores it together with se_set_counters. */
     struct se_done_rec* done_recs; /* auto-reset done lists: 2 * segments * seg_stride records
                                       (se_done_layout), double-buffered by step parity */
-    int32_t* done_count;           /* auto-reset per-segment counts: 2 * segments entries */
+    int32_t* done_count;           /* auto-reset per-segment counts: 2 * segments entries. se_bind
+                                      (auto-reset) and se_set_counters (whenever it is bound) clear
+                                      them with a synchronous memset; a step writes all `segments`
+                                      counts of its parity half and nothing of the other half */
     double* reward64;              /* optional (NULL): the reference's f64 reward, unrounded */
 } se_state;
 
 /* One replayed MOVE's variates (the draws the reference made through `random`,
- * SURVEY.md Appendix A); used by se_step_replay only. 48 bytes. A variate the
+ * SURVEY.md Appendix A); used by se_step_replay only. 40 bytes, no padding; the replaying
+ * calls read the first 36 and write `used` alone. A variate the
  * step needs but the record lacks (NaN, or arrive_dest < 0) yields
  * SE_ERR_NEED_DRAW and no state change: a caller holding the reference's RNG
  * draws exactly that next variate and steps again (shipping.Environment does). */
@@ -146,7 +153,9 @@ int se_set_ports(se_env* env, int32_t P, const int32_t* port_x, const int32_t* p
 int se_bind(se_env* env, const se_state* state);
 
 /* reset() (environment.py:227-243) for every env with mask[i] != 0 (mask NULL = all):
- * cargo 0, fuel 200, origin ~ U{0..P-1}, dest ~ U{others}, ship at the origin port.
+ * cargo 0, fuel 200, origin ~ U{0..P-1}, dest ~ U{others}, ship at the origin port; reward,
+ * done, err and ep_return 0, ep_start the step counter. An env with mask[i] == 0 keeps every
+ * byte of every field, reward, done and err included; the done lists are not touched.
  * Draws: Philox(seed, env) at counter (reset epoch, slot 5); the epoch advances per call. */
 int se_reset(se_env* env, const uint8_t* mask, void* stream);
 
@@ -162,7 +171,8 @@ int se_reset_to(se_env* env, const uint8_t* mask, const int32_t* origin, const i
 int se_step(se_env* env, const int32_t* actions, void* stream);
 
 /* `steps` consecutive steps issued from native code: step k takes its actions from
- * actions + k * ld (ld >= n int32 entries, 16-byte aligned rows), for a fixed action
+ * actions + k * ld (ld >= n int32 entries, 16-byte aligned rows; the ld - n entries behind a
+ * row's n are neither read nor written), for a fixed action
  * schedule (a rollout of a pre-computed policy, the bench's timed region).
  * Guaranteed: the final state (x, y, fuel, cargo, origin, dest), the last step's reward, done
  * and err, and the step counter equal `steps` se_step calls on the same rows, bit for bit.
@@ -281,7 +291,8 @@ int se_host_reset_to(se_host* h, int64_t n, const se_state* st, const uint8_t* m
                      const int32_t* origin, const int32_t* dest);
 int se_host_destroy(se_host* h);
 
-/* utils.preprocessing.preprocess_state rows (:25-62) as f32, row stride ld >= 6+4P:
+/* utils.preprocessing.preprocess_state rows (:25-62) as f32, n rows of 6+4P entries at row
+ * stride ld >= 6+4P (the ld - (6+4P) entries behind a row are not written; the state is only read):
  * [x, y, fuel, fuel ("cargo" is self.fuel, environment.py:206), origin, dest, (px,py,pfuel,pcargo)*P],
  * None -> -1. */
 int se_observe(se_env* env, float* obs, int64_t ld, void* stream);
@@ -290,7 +301,8 @@ int se_observe(se_env* env, float* obs, int64_t ld, void* stream);
  * packed MSB-first per row (numpy.packbits order), row stride ceil((4+P+250)/8) bytes. */
 int se_valid_mask(se_env* env, uint8_t* bits, void* stream);
 
-/* Synthetic agent: fills actions[i] from Philox(seed, env) at (t, slot 6) with the
+/* Synthetic agent: fills actions[i] (n entries; the state is neither read nor written) from
+ * Philox(seed, env) at (t, slot 6) with the
  * bench mix (90% move, 5% take cargo U{1..20}, 3% take fuel U{1..20}, 2% select). */
 int se_gen_actions(se_env* env, int32_t* actions, uint32_t t, void* stream);
 
@@ -596,7 +608,9 @@ int se_sarsa_bind(se_sarsa* s, double* q, const se_sarsa_state* st);
  * epsilon = 0: test_policy's greedy evaluation). Outputs (device, n entries): reward, the
  * counted step's f64 reward (0 where status != OK); ended, 1 where the episode restarted;
  * status, SE_SARSA_*; fin_return / fin_len, the finished episode's return and length where
- * ended. max_attempts in 1..64. The env's step counter advances by one. n = 0: a no-op. */
+ * ended. max_attempts in 1..64. The env's step counter advances by one. n = 0: a no-op. Beside
+ * the table, the se_sarsa_state fields and the outputs (n entries each) it writes the env's
+ * bound state as a step and a reset of the restarted envs do; the done lists are not touched. */
 int se_sarsa_step(se_sarsa* s, double lr, double gamma, double epsilon, int32_t learn, int32_t max_steps,
                   int32_t max_attempts, uint32_t t, double* reward, uint8_t* ended, int32_t* status,
                   double* fin_return, int32_t* fin_len, void* stream);
@@ -624,7 +638,8 @@ int se_qnet_create(se_qnet** out, se_env* env);
  * env itself stays usable (se_qtrain_create has the same limit). */
 int se_qnet_set_weights(se_qnet* q, const float* w1, const float* b1, const float* w2,
                         const float* b2, const float* w3, const float* b3, void* stream);
-/* actions[i]: the agent-index action (se_step input) for every env. Exploration draws
+/* actions[i]: the agent-index action (se_step input) for every env, n entries; the env's
+ * state is only read. Exploration draws
  * Philox(seed, env) at (t, slot 14): word 0 * 2^-32 <= epsilon explores, and word 1
  * picks the k-th valid action (ascending index) uniformly. q_out (optional, NULL):
  * the Q rows as computed, [n][ldq] f32, ldq >= A. */
@@ -651,7 +666,8 @@ typedef struct se_replay se_replay;
 int se_replay_create(se_replay** out, se_env* env, int64_t capacity);
 /* Record s and the agent-index actions of every env: call right before se_step. */
 int se_replay_begin(se_replay* r, const int32_t* actions, void* stream);
-/* Record reward, done and s' after se_step: appends n transitions (FIFO eviction). A
+/* Record reward, done and s' after se_step: appends n transitions (FIFO eviction; the ring
+ * never holds more than `capacity`, whether or not capacity is a multiple of n or of 4). A
  * step that raised (err != 0) is stored flagged and never sampled: the reference's loop
  * breaks before remember (:304-309). cut (optional, device u8[n]): 1 where the episode must
  * restart, i.e. the step raised or the episode length (step counter - ep_start) >= max_steps (max_steps > 0 needs an auto-reset
@@ -670,7 +686,8 @@ int se_replay_end_reset(se_replay* r, uint8_t* cut, int32_t max_steps, void* str
  * ring's reward / done / s' record and restarts the cut envs from the state it holds
  * (env.step + remember + env.reset of the training loop, agents/dqn.py:281-309). Needs an
  * auto-reset env; when n, the ring head / capacity are not multiples of 4 or cut is not
- * 4-byte aligned it makes the two launches instead. Results are identical either way. */
+ * 4-byte aligned it makes the two launches instead. Results are identical either way.
+ * cut (required here): n bytes, every one written (0 or 1). */
 int se_step_record(se_replay* r, const int32_t* actions, uint8_t* cut, int32_t max_steps, void* stream);
 int se_replay_size(se_replay* r, int64_t* size, int64_t* capacity);
 /* A minibatch of `batch` distinct transitions: batch position j takes logical index
@@ -766,11 +783,14 @@ int se_clear_stats(se_env* env, void* stream);
  * done_count buffers must be sized for (2 * segments * seg_stride records,
  * 2 * segments counts). se_done_list gives where the most recent step wrote
  * (record offset of its buffer, offset of its counts); that list stays intact
- * while the following step runs. Only the first done_count[s] records of segment s
+ * while the following step runs (a step writes nothing of the other half, neither
+ * records nor counts). Only the first done_count[s] records of segment s
  * are valid: records past the count may be stale, or filler records (env == -1,
  * step == the step counter) that pad a segment's records to whole 128-byte lines
  * (above 2^23 envs, or SHIPENV_DONE_PAD=1 at se_create). se_done_compact copies the
- * valid records contiguously (out: up to n records, out_count: 1 int) on the stream. */
+ * valid records contiguously on the stream: exactly *out_count records of out, at most n (an
+ * out of n records suffices; the records behind them are not written), and the one int
+ * out_count. se_episode_stats writes its three doubles. Neither writes a bound buffer. */
 int se_done_layout(se_env* env, int64_t* seg_stride, int32_t* segments);
 int se_done_list(se_env* env, int64_t* rec_offset, int64_t* count_offset);
 int se_done_compact(se_env* env, se_done_rec* out, int32_t* out_count, void* stream);

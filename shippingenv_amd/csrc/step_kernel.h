@@ -248,6 +248,10 @@ __device__ __forceinline__ void step_tail_envs(const StepArgs& A, const LdsWorld
             if ((F.mask >> j) & 1u)
                 A.done_recs[b * A.seg + c++] = se_done_rec{(int32_t)(at.base + j), F.ret[j], F.len[j], (int32_t)A.t};
         A.done_count[b] = c;
+        // fewer than 4 envs: step_kernel did not run, so the other waves' segments of the one
+        // workgroup (se_done_layout still counts them) get their count of this step here
+        if (A.n < kEnvsPerThread)
+            for (int s = 1; s < kStepBlock / 64; ++s) A.done_count[s] = 0;
         if (bs.eps != 0) {
             // the slab entry of the wave that owns group g
             const int64_t bl = g / (A.iters * kStepBlock), wv = (g % kStepBlock) >> 6;

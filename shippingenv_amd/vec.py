@@ -133,7 +133,7 @@ class VecEnv:
         self.done_seg, self.done_segments = seg.value, nseg.value
         nrec = 2 * self.done_seg * self.done_segments if self.auto_reset else 1
         self.done_recs = torch.zeros((nrec, 4), dtype=torch.int32, **kw)
-        self.done_count = torch.zeros(max(2 * self.done_segments, 4), dtype=torch.int32, **kw)
+        self.done_count = torch.zeros(max(2 * self.done_segments, 1), dtype=torch.int32, **kw)
         self._done_out = None
         self._state = N.SeState(*[t.data_ptr() for t in (
             self.x, self.y, self.fuel, self.cargo, self.origin, self.dest, self.reward,
@@ -422,7 +422,7 @@ class VecEnv:
         """Episodes finished by the last step (auto-reset), in env order:
         (env, ep_return, ep_len, step) tensors."""
         if self._done_out is None:
-            self._done_out = torch.empty((self.n + 4, 4), dtype=torch.int32, device=self.device)
+            self._done_out = torch.empty((max(self.n, 1), 4), dtype=torch.int32, device=self.device)
             self._done_cnt = torch.empty(1, dtype=torch.int32, device=self.device)
         N.check(N.lib().se_done_compact(self._h, _ptr(self._done_out), _ptr(self._done_cnt),
                                         self._stream()))
