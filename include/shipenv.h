@@ -620,6 +620,63 @@ int se_sarsa_choose(se_sarsa* s, double epsilon, uint32_t t, int32_t* type, int3
                     void* stream);
 int se_sarsa_destroy(se_sarsa* s);
 
+/* The sparse table: a second kind of handle behind the same se_sarsa_step / se_sarsa_choose, for
+ * worlds whose dense table does not fit (rows grows with (P + 1)^2). It holds a page of A doubles
+ * for every row some update has met and nothing for the others; since the dense table starts as
+ * zeros, an absent row IS a row of zeros, and a sparse learner computes what the dense one does,
+ * bit for bit: every output, the env state, the learner state, and the table as a map.
+ *
+ * Layout (caller-owned device memory, like the dense q):
+ *   keys:  int64_t[capacity]; -1 is an empty slot, any other value the dense layout's row number.
+ *   pages: double[capacity * A]; pages[s * A + slot] is entry (keys[s], slot) of the dense layout.
+ *          Zero-initialised by the caller; the pages of empty slots stay zero.
+ *   capacity: a power of two >= 64.
+ *   home(row) = mix(row) & (capacity - 1), mix the splitmix64 finaliser on the row as uint64_t:
+ *          z ^= z >> 30;  z *= 0xbf58476d1ce4e5b9;
+ *          z ^= z >> 27;  z *= 0x94d049bb133111eb;
+ *          z ^= z >> 31.
+ *   Probing is linear with step 1 and wraps from the last slot to slot 0. Nothing is deleted: a
+ *   lookup ends at the row, at the first empty slot (the row is absent), or after capacity slots.
+ * A caller may preload a table that holds these rules (every key reachable from its home before
+ * an empty slot, no key twice) before se_sarsa_bind_sparse.
+ *
+ * A step reads the table as the step before left it: a missing row's greedy scan answers
+ * SELECT 0, its curr_q and next_q are 0.0. With learn != 0 every update then finds its row's
+ * page or takes the first empty slot of the row's probe for it (a 64-bit compare-and-swap of -1
+ * with the row), and the lowest local env index wins each entry as in the dense kind. An update
+ * whose probe finds all capacity slots taken by other rows is dropped and counted; it neither
+ * waits nor writes. Where two new rows race for one slot in a step, which of them takes it is a
+ * matter of timing: the placement of rows is not reproducible, the table as a map row -> page
+ * is. learn = 0 changes no byte of keys or pages. The handle owns capacity * A claim words, n
+ * parked updates and the two counters. */
+/* As se_sarsa_create (the same refusals, the same layout from se_sarsa_layout: the virtual rows,
+ * A, cmax), for a table of `capacity` rows. SE_EINVAL for a capacity that is not a power of two
+ * >= 64 or where capacity * A * 12 overflows int64. Allocates capacity * A * 4 + n * 20 + 16
+ * bytes on the env's device (nothing for n = 0). */
+int se_sarsa_create_sparse(se_sarsa** out, se_env* env, int64_t capacity);
+/* keys: capacity entries, pages: capacity * A doubles on the env's device; the struct is copied;
+ * the buffers stay the caller's. Counts the occupied slots of keys into `used` (one launch over
+ * keys on the null stream, which it synchronises: whatever wrote keys must have finished);
+ * `dropped` is kept. Reads keys, writes no caller memory. se_sarsa_bind on a sparse handle and
+ * se_sarsa_bind_sparse on a dense one return SE_EINVAL. */
+int se_sarsa_bind_sparse(se_sarsa* s, int64_t* keys, double* pages, const se_sarsa_state* st);
+/* capacity, the pages taken (occupied slots) and the updates dropped since create, after
+ * everything queued on the stream: it synchronises the stream. Any output may be NULL. Reads no
+ * caller memory. */
+int se_sarsa_sparse_stats(se_sarsa* s, int64_t* capacity, int64_t* used, int64_t* dropped, void* stream);
+/* Moves the table into new buffers of new_capacity slots (a power of two >= 64; smaller than the
+ * current one is legal while it holds the `used` rows, else SE_EINVAL), which the caller has set
+ * to -1 (new_keys, new_capacity entries) and zero (new_pages, new_capacity * A doubles): one
+ * launch over the old slots re-inserts every occupied row and copies its page, then the handle
+ * takes new claim words (new_capacity * A * 4 bytes, the old ones are freed) and binds the new
+ * buffers. `used` carries over, `dropped` is kept. It synchronises the stream before and after.
+ * The old keys and pages are only read, and never touched again by the handle; of the new
+ * buffers only the slots and pages of the rows moved are written. */
+int se_sarsa_sparse_grow(se_sarsa* s, int64_t* new_keys, double* new_pages, int64_t new_capacity, void* stream);
+/* Host only, no device, no handle: home(row) for a table of `capacity` slots; -1 for a negative
+ * row or a capacity that is not a power of two >= 64. */
+int64_t se_sarsa_sparse_home(int64_t row, int64_t capacity);
+
 /* DQN policy step fused on the GPU (agents/dqn.py): DQNNetwork 6+4P -> 128 -> 128 -> A
  * (A = 4+P+250, :21-33) evaluated with bf16 MFMA and f32 accumulation on the
  * observation preprocess_state builds (utils/preprocessing.py:25-62; its constant port

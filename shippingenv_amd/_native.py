@@ -85,7 +85,7 @@ _LIB = None
 
 
 # Every symbol include/shipenv.h declares, with its argument types. The result type is int (a
-# status) but for the two in _RESTYPES.
+# status) but for those in _RESTYPES.
 _P, _i32, _i64, _u32, _u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
 SIGNATURES = {
     "se_create": [C.POINTER(_P), C.c_int, _i64, _i64, _i32, _i32, _P, _i32, _P, _P, _P, _P, _u64, _u32],
@@ -122,6 +122,11 @@ SIGNATURES = {
     "se_sarsa_step": [_P, C.c_double, C.c_double, C.c_double, _i32, _i32, _i32, _u32, _P, _P, _P, _P, _P, _P],
     "se_sarsa_choose": [_P, C.c_double, _u32, _P, _P, _P, _P],
     "se_sarsa_destroy": [_P],
+    "se_sarsa_create_sparse": [C.POINTER(_P), _P, _i64],
+    "se_sarsa_bind_sparse": [_P, _P, _P, C.POINTER(SeSarsaState)],
+    "se_sarsa_sparse_stats": [_P, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _P],
+    "se_sarsa_sparse_grow": [_P, _P, _P, _i64, _P],
+    "se_sarsa_sparse_home": [_i64, _i64],
     "se_qnet_create": [C.POINTER(_P), _P],
     "se_qnet_set_weights": [_P, _P, _P, _P, _P, _P, _P, _P],
     "se_policy": [_P, _P, C.c_double, _u32, _P, _i64, _P],
@@ -173,7 +178,7 @@ SIGNATURES = {
     "se_last_error": [],
     "se_abi_version": [],
 }
-_RESTYPES = {"se_last_error": C.c_char_p, "se_qtrain_grad_size": _i64}
+_RESTYPES = {"se_last_error": C.c_char_p, "se_qtrain_grad_size": _i64, "se_sarsa_sparse_home": _i64}
 EXPORTS = tuple(SIGNATURES)
 
 

@@ -1,7 +1,10 @@
 #pragma once
-// sarsa.h — batched tabular SARSA (agents/sarsa.py): one learner, one dense f64 Q-table in
-// HBM, n envs. The table's layout, the discretiser, the greedy scan, the two kernels of a
-// vector step, and se_sarsa_create / _layout / _bind / _step / _choose / _destroy.
+// sarsa.h — batched tabular SARSA (agents/sarsa.py): one learner, one f64 Q-table in HBM, n
+// envs. The table's layout, the discretiser, the greedy scan, the kernels of a vector step, and
+// se_sarsa_create / _layout / _bind / _step / _choose / _destroy. The table is dense (every
+// row of the layout) or sparse (se_sarsa_create_sparse / _bind_sparse / _sparse_stats /
+// _sparse_grow / _sparse_home: a hash table of the rows met); the step and choose kernels are
+// templates over the table accessor, SarsaDense or SarsaSparse.
 //
 // A fragment of shipenv.hip's translation unit, included at its end after mcts.h: not a
 // stand-alone header. Uses world.h (WorldDims, LdsWorld, stage_world), env_core.h (EnvArgs, Ship,
@@ -50,10 +53,23 @@
 //
 // Many envs, one table: every Q read of vector step k sees the table after all writes of
 // step k-1, and where several envs update one entry in a step the lowest env index wins and
-// the others' updates are dropped. Two launches: sarsa_step_kernel reads the table and writes
-// none of it, claims owner[entry] with a 32-bit atomicMin of the env index and parks (entry,
-// new value); sarsa_commit_kernel writes where the claim is its own and sets the claim word
-// back to empty, so the claim table is never cleared. No float atomics, bit-reproducible.
+// the others' updates are dropped. The dense kind's two launches: sarsa_step_kernel reads the
+// table and writes none of it, claims owner[entry] with a 32-bit atomicMin of the env index and
+// parks (entry, new value); sarsa_commit_kernel writes where the claim is its own and sets the
+// claim word back to empty, so the claim table is never cleared. No float atomics,
+// bit-reproducible.
+//
+// The sparse table (include/shipenv.h has the contract): keys[capacity] holds -1 or a row
+// number, pages[s * A ..] that row's A doubles, the home bucket is the splitmix64 finaliser of the
+// row masked to the capacity, probing linear and wrapping, nothing is deleted. An absent row
+// reads as zeros: its greedy scan answers SELECT 0 and its curr_q / next_q are 0.0. The step
+// kernel looks each of its two states' rows up at most once, reads only, and parks (row, slot,
+// new value); with learn != 0 sarsa_claim_kernel then finds or inserts every parked row (a
+// 64-bit atomicCAS of -1 -> row, at most `capacity` slots: a full table drops the update, unparks
+// it and counts it), rewrites the parked row to the page's entry and claims it with the same
+// atomicMin; sarsa_commit_kernel is the dense one on `pages`. Launch boundaries order it all: no
+// page is read in the kernel that inserts its key. Which slot a row takes when two new rows race
+// for a bucket depends on timing; the table as a map of row -> page does not.
 //
 // Draw contract: key (seed, env_id_base + i), the t word the caller's vector-step
 // number. Slot 20: word 0 the explore uniform of next_action, word 1 its sample_action word,
@@ -117,16 +133,82 @@ __device__ __forceinline__ void sarsa_action(int P, int cmax, int slot, int& typ
     }
 }
 
-// choose_action (:135-165) on ship s: wu the explore word, ws the sample_action word. A raising
-// sample_action leaves its negative SE_SAMPLE_* type.
-__device__ __forceinline__ void sarsa_choose(const LdsWorld& w, const double* __restrict__ q, int A, int cmax,
-                                             const Ship& s, double epsilon, uint32_t wu, uint32_t ws, int& type,
-                                             int& a, int& b) {
+// the splitmix64 finaliser: the sparse table's hash of a row number
+__host__ __device__ __forceinline__ uint64_t sarsa_mix(uint64_t z) {
+    z ^= z >> 30;
+    z *= 0xbf58476d1ce4e5b9ull;
+    z ^= z >> 27;
+    z *= 0x94d049bb133111ebull;
+    z ^= z >> 31;
+    return z;
+}
+
+// The table accessors. find(row, A) answers the row's A doubles, null where the table does not
+// hold the row (the dense table holds every row); read(page, k) is entry k of a found page.
+struct SarsaDense {
+    static constexpr bool kSparse = false;
+    const double* q;
+    __device__ __forceinline__ const double* find(int64_t row, int A) const { return q + row * A; }
+    static __device__ __forceinline__ double read(const double* page, int k) { return page[k]; }
+};
+
+struct SarsaSparse {
+    static constexpr bool kSparse = true;
+    const int64_t* keys;
+    const double* pages;
+    int64_t mask;         // capacity - 1
+    int32_t* park_slot;   // [n] the parked update's slot; its row goes to park_entry
+    __device__ __forceinline__ const double* find(int64_t row, int A) const {
+        int64_t s = (int64_t)(sarsa_mix((uint64_t)row) & (uint64_t)mask);
+        for (int64_t k = 0; k <= mask; ++k) {  // a full table without the row ends here
+            const int64_t key = keys[s];
+            if (key == row) return pages + s * A;
+            if (key < 0) return nullptr;
+            s = (s + 1) & mask;
+        }
+        return nullptr;
+    }
+    static __device__ __forceinline__ double read(const double* page, int k) { return page ? page[k] : 0.0; }
+};
+
+// One state's row, looked up at most once (the dense address is arithmetic: nothing to keep).
+template <class T>
+struct SarsaRow {
+    const T& table;
+    int64_t row;
+    int A;
+    const double* page = nullptr;
+    bool looked = false;
+    __device__ __forceinline__ SarsaRow(const T& t, int64_t r, int a) : table(t), row(r), A(a) {}
+    __device__ __forceinline__ const double* get() {
+        if constexpr (!T::kSparse) {
+            return table.find(row, A);
+        } else {
+            if (!looked) {
+                page = table.find(row, A);
+                looked = true;
+            }
+            return page;
+        }
+    }
+};
+
+// choose_action (:135-165) on ship s, whose row is r: wu the explore word, ws the sample_action
+// word. A raising sample_action leaves its negative SE_SAMPLE_* type.
+template <class T>
+__device__ __forceinline__ void sarsa_choose(const LdsWorld& w, SarsaRow<T>& r, int cmax, const Ship& s,
+                                             double epsilon, uint32_t wu, uint32_t ws, int& type, int& a, int& b) {
     if (u32(wu) < epsilon) {
         sample_action(w, s, ws, type, a, b);
         return;
     }
-    const double* row = q + sarsa_row(w, s) * A;
+    const double* row = r.get();
+    if constexpr (T::kSparse) {
+        if (!row) {  // a row of zeros: 0.0 > -inf at SELECT 0, and nothing after it is greater
+            sarsa_action(w.P, cmax, 0, type, a, b);
+            return;
+        }
+    }
     int best = -1;
     double best_q = -__builtin_inf();
     const int head = w.P + 4;
@@ -163,10 +245,11 @@ __device__ __forceinline__ void sarsa_choose(const LdsWorld& w, const double* __
     sarsa_action(w.P, cmax, best, type, a, b);
 }
 
+template <class T>
 struct SarsaArgs : EnvArgs {
     uint32_t t;
     se_sarsa_state ag;
-    const double* q;
+    T table;
     uint32_t* owner;
     int32_t A, cmax;
     double lr, gamma, epsilon;
@@ -184,7 +267,8 @@ __device__ __forceinline__ int32_t sarsa_raise_status(int type) {
     return type == SE_SAMPLE_NO_OTHER_PORT ? SE_SARSA_NEVER_RETURNS : SE_SARSA_RAISED;
 }
 
-__global__ __launch_bounds__(kBlock) void sarsa_step_kernel(SarsaArgs A) {
+template <class T>
+__global__ __launch_bounds__(kBlock) void sarsa_step_kernel(SarsaArgs<T> A) {
     extern __shared__ uint32_t lds[];
     const LdsWorld w = stage_world(A.world, A.dims, lds);
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * kBlock) {
@@ -196,11 +280,12 @@ __global__ __launch_bounds__(kBlock) void sarsa_step_kernel(SarsaArgs A) {
         const U4 c = draw(key, A.t, kSlotSarsa);
         int32_t status = SE_SARSA_OK;
         // a pending action the table has no slot for was never chosen here: the env is fresh
+        SarsaRow<T> r0(A.table, sarsa_row(w, s), A.A);  // the state before
         if (A.ag.fresh[i] || sarsa_slot(w.P, A.cmax, ty, va, vb) < 0) {
-            sarsa_choose(w, A.q, A.A, A.cmax, s, A.epsilon, c.v[2], c.v[3], ty, va, vb);  // :256
+            sarsa_choose(w, r0, A.cmax, s, A.epsilon, c.v[2], c.v[3], ty, va, vb);  // :256
             if (ty < 0) status = sarsa_raise_status(ty);
         }
-        const int64_t entry = status == SE_SARSA_OK ? sarsa_row(w, s) * A.A + sarsa_slot(w.P, A.cmax, ty, va, vb) : -1;
+        const int slot0 = status == SE_SARSA_OK ? sarsa_slot(w.P, A.cmax, ty, va, vb) : -1;
         // _try_action (:201-220)
         double reward = 0.0;
         bool dead = false, stepped = false;
@@ -227,17 +312,24 @@ __global__ __launch_bounds__(kBlock) void sarsa_step_kernel(SarsaArgs A) {
         int64_t parked = -1;
         if (status == SE_SARSA_OK) {
             int nty, na, nb;
-            sarsa_choose(w, A.q, A.A, A.cmax, s, A.epsilon, c.v[0], c.v[1], nty, na, nb);  // :263
+            SarsaRow<T> r1(A.table, sarsa_row(w, s), A.A);  // the state after
+            sarsa_choose(w, r1, A.cmax, s, A.epsilon, c.v[0], c.v[1], nty, na, nb);  // :263
             if (nty < 0) {
                 status = sarsa_raise_status(nty);
             } else {
                 if (A.learn) {  // update (:187-195)
-                    const double curr_q = A.q[entry];
-                    const double next_q = A.q[sarsa_row(w, s) * A.A + sarsa_slot(w.P, A.cmax, nty, na, nb)];
+                    const double curr_q = T::read(r0.get(), slot0);
+                    const double next_q = T::read(r1.get(), sarsa_slot(w.P, A.cmax, nty, na, nb));
                     const double target = reward + A.gamma * next_q;
                     A.park_val[i] = curr_q + A.lr * (target - curr_q);
-                    atomicMin(A.owner + entry, (uint32_t)i);
-                    parked = entry;
+                    if constexpr (T::kSparse) {  // sarsa_claim_kernel finds the page and claims
+                        A.table.park_slot[i] = slot0;
+                        parked = r0.row;
+                    } else {
+                        const int64_t entry = r0.row * A.A + slot0;
+                        atomicMin(A.owner + entry, (uint32_t)i);
+                        parked = entry;
+                    }
                 }
                 ty = nty;
                 va = na;
@@ -284,9 +376,92 @@ __global__ __launch_bounds__(kBlock) void sarsa_commit_kernel(int64_t n, const i
     }
 }
 
+// The sparse table's claim: every parked (row, slot) finds its row's page or takes the first
+// empty slot of the row's probe for it, then claims the page's entry as the dense step kernel
+// claims its own and parks that entry for sarsa_commit_kernel. counters[0] counts the pages
+// taken, counters[1] the updates dropped because all `mask + 1` slots held other rows.
+__global__ __launch_bounds__(kBlock) void sarsa_claim_kernel(int64_t n, int64_t* keys, int64_t mask, int32_t A,
+                                                             int64_t* park_entry, const int32_t* __restrict__ park_slot,
+                                                             uint32_t* owner, unsigned long long* counters) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const int64_t row = park_entry[i];
+        if (row < 0) continue;
+        int64_t s = (int64_t)(sarsa_mix((uint64_t)row) & (uint64_t)mask), page = -1;
+        for (int64_t k = 0; k <= mask; ++k) {
+            int64_t old = __hip_atomic_load(keys + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (old < 0) {
+                old = (int64_t)atomicCAS((unsigned long long*)(keys + s), ~0ull, (unsigned long long)row);
+                if (old < 0) {
+                    atomicAdd(counters, 1ull);
+                    old = row;
+                }
+            }
+            if (old == row) {
+                page = s;
+                break;
+            }
+            s = (s + 1) & mask;
+        }
+        if (page < 0) {  // no room: the update is lost, and counted
+            park_entry[i] = -1;
+            atomicAdd(counters + 1, 1ull);
+            continue;
+        }
+        const int64_t e = page * A + park_slot[i];
+        park_entry[i] = e;
+        atomicMin(owner + e, (uint32_t)i);
+    }
+}
+
+// keys[0 .. capacity) -> counters[0] += the occupied slots (se_sarsa_bind_sparse)
+__global__ __launch_bounds__(kBlock) void sarsa_count_kernel(const int64_t* __restrict__ keys, int64_t capacity,
+                                                             unsigned long long* counters) {
+    unsigned long long mine = 0;
+    for (int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x; s < capacity; s += (int64_t)gridDim.x * kBlock)
+        mine += keys[s] >= 0;
+    if (mine) atomicAdd(counters, mine);
+}
+
+// se_sarsa_sparse_grow: a block takes kBlock old slots at a time; every occupied one takes the
+// first empty slot of its row's probe in the new keys (the rows are distinct, the new table has
+// room for all of them: each finds one), then the block copies the pages, A doubles each, with
+// consecutive threads on consecutive doubles.
+__global__ __launch_bounds__(kBlock) void sarsa_grow_kernel(const int64_t* __restrict__ keys,
+                                                            const double* __restrict__ pages, int64_t capacity,
+                                                            int64_t* new_keys, double* new_pages, int64_t new_mask,
+                                                            int32_t A) {
+    __shared__ int64_t to[kBlock];
+    for (int64_t base = (int64_t)blockIdx.x * kBlock; base < capacity; base += (int64_t)gridDim.x * kBlock) {
+        const int64_t s = base + threadIdx.x;
+        int64_t dst = -1;
+        const int64_t row = s < capacity ? keys[s] : -1;
+        if (row >= 0) {
+            int64_t d = (int64_t)(sarsa_mix((uint64_t)row) & (uint64_t)new_mask);
+            for (int64_t k = 0; k <= new_mask; ++k) {
+                if (__hip_atomic_load(new_keys + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0 &&
+                    (int64_t)atomicCAS((unsigned long long*)(new_keys + d), ~0ull, (unsigned long long)row) < 0) {
+                    dst = d;
+                    break;
+                }
+                d = (d + 1) & new_mask;
+            }
+        }
+        to[threadIdx.x] = dst;
+        __syncthreads();
+        const int64_t span = (int64_t)kBlock * A;
+        for (int64_t j = threadIdx.x; j < span; j += kBlock) {
+            const int64_t lane = j / A, k = j - lane * A;
+            const int64_t d = to[lane];
+            if (d >= 0) new_pages[d * A + k] = pages[(base + lane) * A + k];
+        }
+        __syncthreads();
+    }
+}
+
+template <class T>
 struct SarsaChooseArgs : EnvArgs {
     uint32_t t;
-    const double* q;
+    T table;
     int32_t A, cmax;
     double epsilon;
     int32_t* type;
@@ -294,14 +469,16 @@ struct SarsaChooseArgs : EnvArgs {
     int32_t* b;
 };
 
-__global__ __launch_bounds__(kBlock) void sarsa_choose_kernel(SarsaChooseArgs A) {
+template <class T>
+__global__ __launch_bounds__(kBlock) void sarsa_choose_kernel(SarsaChooseArgs<T> A) {
     extern __shared__ uint32_t lds[];
     const LdsWorld w = stage_world(A.world, A.dims, lds);
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * kBlock) {
         const Ship s = load_ship(A.st, i);
         const U4 c = draw(env_key(A.seed, A.env_base + i), A.t, kSlotSarsa);
         int ty, va, vb;
-        sarsa_choose(w, A.q, A.A, A.cmax, s, A.epsilon, c.v[2], c.v[3], ty, va, vb);
+        SarsaRow<T> r(A.table, sarsa_row(w, s), A.A);
+        sarsa_choose(w, r, A.cmax, s, A.epsilon, c.v[2], c.v[3], ty, va, vb);
         A.type[i] = ty;
         A.a[i] = va;
         A.b[i] = vb;
@@ -316,12 +493,19 @@ struct se_sarsa {
     uint64_t world_version = 0;  // of the world the layout was made for
     int64_t n = 0, rows = 0;
     int32_t A = 0, cmax = 0;
-    uint32_t* d_owner = nullptr;  // [rows * A] claim words, kSarsaNoOwner between steps
+    uint32_t* d_owner = nullptr;  // [rows * A] (sparse: [capacity * A]) claim words, kSarsaNoOwner between steps
     int64_t* d_park_entry = nullptr;  // [n]
     double* d_park_val = nullptr;     // [n]
     double* q = nullptr;
     se_sarsa_state ag{};
     bool bound = false;
+    // the sparse kind
+    bool sparse = false;
+    int64_t capacity = 0;
+    int64_t* keys = nullptr;   // the caller's, [capacity]
+    double* pages = nullptr;   // the caller's, [capacity * A]
+    int32_t* d_park_slot = nullptr;            // [n]
+    unsigned long long* d_counters = nullptr;  // used, dropped
 };
 
 namespace {
@@ -337,31 +521,24 @@ int sarsa_ready(se_sarsa* h, bool need_bind) {
     return SE_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int se_sarsa_create(se_sarsa** out, se_env* env, int64_t max_table_bytes) {
+// what both kinds of create refuse, and the layout of the env's world
+int sarsa_layout_for(se_sarsa** out, se_env* env, int64_t& rows, int64_t& A, int& cmax) {
     if (!out) return fail(SE_EINVAL, "null out");
     *out = nullptr;
     int rc = check_ready(env);
     if (rc) return rc;
     if (env->dims.P < 1) return fail(SE_EINVAL, "SARSA needs at least one port");
     if (env->n >= (int64_t)kSarsaNoOwner) return fail(SE_EINVAL, "SARSA takes fewer than 2^32 - 1 envs");
-    if (max_table_bytes < 0) return fail(SE_EINVAL, "max_table_bytes must be >= 0");
     const int P = env->dims.P;
-    const int cmax = std::max(20, env->stock_cargo_max);
-    const int64_t A = (int64_t)P + 4 + cmax + 20;
+    cmax = std::max(20, env->stock_cargo_max);
+    A = (int64_t)P + 4 + cmax + 20;
     if (A > INT32_MAX) return fail(SE_EINVAL, "a port's cargo stock is too large for a SARSA table");
-    // rows * A entries of 8 bytes and a 4-byte claim word each; the products stay far below 2^63
-    // (H, W <= 256, P <= 254, stocks < 2^31), but the bytes may exceed what a device holds
-    const int64_t rows = (int64_t)env->dims.H * env->dims.W * kSarsaClasses * (P + 1) * (P + 1);
-    int64_t entries, bytes;
-    if (__builtin_mul_overflow(rows, A, &entries) || __builtin_mul_overflow(entries, (int64_t)12, &bytes))
-        return fail(SE_EINVAL, "the SARSA table's size overflows int64");
-    if (bytes > max_table_bytes)
-        return fail(SE_EINVAL, "the SARSA table and its claim words need " + std::to_string(bytes) +
-                                   " bytes, more than max_table_bytes");
+    rows = (int64_t)env->dims.H * env->dims.W * kSarsaClasses * (P + 1) * (P + 1);
+    return SE_OK;
+}
+
+// the handle with `entries` claim words and the parking places (none of it for n = 0)
+int sarsa_new(se_sarsa** out, se_env* env, int64_t rows, int64_t A, int cmax, int64_t entries, int64_t capacity) {
     se_sarsa* h = new se_sarsa;
     h->env = env;
     h->device = env->device;
@@ -370,6 +547,8 @@ int se_sarsa_create(se_sarsa** out, se_env* env, int64_t max_table_bytes) {
     h->rows = rows;
     h->A = (int32_t)A;
     h->cmax = cmax;
+    h->sparse = capacity > 0;
+    h->capacity = capacity;
     DeviceGuard g(env->device);
     hipError_t e = hipSuccess;
     if (h->n > 0) {
@@ -377,6 +556,11 @@ int se_sarsa_create(se_sarsa** out, se_env* env, int64_t max_table_bytes) {
         if (e == hipSuccess) e = hipMemset(h->d_owner, 0xff, (size_t)entries * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc(&h->d_park_entry, (size_t)h->n * sizeof(int64_t));
         if (e == hipSuccess) e = hipMalloc(&h->d_park_val, (size_t)h->n * sizeof(double));
+        if (h->sparse) {
+            if (e == hipSuccess) e = hipMalloc(&h->d_park_slot, (size_t)h->n * sizeof(int32_t));
+            if (e == hipSuccess) e = hipMalloc(&h->d_counters, 2 * sizeof(unsigned long long));
+            if (e == hipSuccess) e = hipMemset(h->d_counters, 0, 2 * sizeof(unsigned long long));
+        }
     }
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -385,6 +569,112 @@ int se_sarsa_create(se_sarsa** out, se_env* env, int64_t max_table_bytes) {
     }
     *out = h;
     return SE_OK;
+}
+
+bool sarsa_capacity_ok(int64_t capacity) { return capacity >= 64 && (capacity & (capacity - 1)) == 0; }
+
+// the two device counters on the host, after everything queued on the stream
+int sarsa_counters(se_sarsa* h, hipStream_t s, int64_t& used, int64_t& dropped) {
+    unsigned long long c[2] = {0, 0};
+    if (h->n > 0) {
+        HIP_TRY(hipMemcpyAsync(c, h->d_counters, sizeof(c), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    used = (int64_t)c[0];
+    dropped = (int64_t)c[1];
+    return SE_OK;
+}
+
+template <class T>
+int sarsa_launch_step(se_sarsa* h, const T& table, double* values, double lr, double gamma, double epsilon,
+                      int32_t learn, int32_t max_steps, int32_t max_attempts, uint32_t t, double* reward,
+                      uint8_t* ended, int32_t* status, double* fin_return, int32_t* fin_len, hipStream_t s) {
+    se_env* env = h->env;
+    size_t lds;
+    int rc = world_lds<sarsa_step_kernel<T>>(env, lds);
+    if (rc) return rc;
+    SarsaArgs<T> A{};
+    static_cast<EnvArgs&>(A) = env_args(env);
+    A.t = t;
+    A.ag = h->ag;
+    A.table = table;
+    A.owner = h->d_owner;
+    A.A = h->A;
+    A.cmax = h->cmax;
+    A.lr = lr;
+    A.gamma = gamma;
+    A.epsilon = epsilon;
+    A.learn = learn != 0;
+    A.max_steps = max_steps;
+    A.max_attempts = max_attempts;
+    A.park_entry = h->d_park_entry;
+    A.park_val = h->d_park_val;
+    A.reward = reward;
+    A.ended = ended;
+    A.status = status;
+    A.fin_return = fin_return;
+    A.fin_len = fin_len;
+    sarsa_step_kernel<T><<<grid_for(env->n), kBlock, lds, s>>>(A);
+    HIP_TRY(hipGetLastError());
+    if (A.learn) {
+        if constexpr (T::kSparse) {
+            sarsa_claim_kernel<<<grid_for(env->n), kBlock, 0, s>>>(env->n, h->keys, h->capacity - 1, h->A,
+                                                                   h->d_park_entry, h->d_park_slot, h->d_owner,
+                                                                   h->d_counters);
+            HIP_TRY(hipGetLastError());
+        }
+        sarsa_commit_kernel<<<grid_for(env->n), kBlock, 0, s>>>(env->n, h->d_park_entry, h->d_park_val, values, h->d_owner);
+        HIP_TRY(hipGetLastError());
+    }
+    return SE_OK;
+}
+
+template <class T>
+int sarsa_launch_choose(se_sarsa* h, const T& table, double epsilon, uint32_t t, int32_t* type, int32_t* a,
+                        int32_t* b, hipStream_t s) {
+    se_env* env = h->env;
+    size_t lds;
+    int rc = world_lds<sarsa_choose_kernel<T>>(env, lds);
+    if (rc) return rc;
+    const SarsaChooseArgs<T> A{env_args(env), t, table, h->A, h->cmax, epsilon, type, a, b};
+    sarsa_choose_kernel<T><<<grid_for(env->n), kBlock, lds, s>>>(A);
+    HIP_TRY(hipGetLastError());
+    return SE_OK;
+}
+
+SarsaSparse sarsa_sparse_table(const se_sarsa* h) { return SarsaSparse{h->keys, h->pages, h->capacity - 1, h->d_park_slot}; }
+
+}  // namespace
+
+extern "C" {
+
+int se_sarsa_create(se_sarsa** out, se_env* env, int64_t max_table_bytes) {
+    int64_t rows, A;
+    int cmax;
+    int rc = sarsa_layout_for(out, env, rows, A, cmax);
+    if (rc) return rc;
+    if (max_table_bytes < 0) return fail(SE_EINVAL, "max_table_bytes must be >= 0");
+    // rows * A entries of 8 bytes and a 4-byte claim word each; the products stay far below 2^63
+    // (H, W <= 256, P <= 254, stocks < 2^31), but the bytes may exceed what a device holds
+    int64_t entries, bytes;
+    if (__builtin_mul_overflow(rows, A, &entries) || __builtin_mul_overflow(entries, (int64_t)12, &bytes))
+        return fail(SE_EINVAL, "the SARSA table's size overflows int64");
+    if (bytes > max_table_bytes)
+        return fail(SE_EINVAL, "the SARSA table and its claim words need " + std::to_string(bytes) +
+                                   " bytes, more than max_table_bytes");
+    return sarsa_new(out, env, rows, A, cmax, entries, 0);
+}
+
+int se_sarsa_create_sparse(se_sarsa** out, se_env* env, int64_t capacity) {
+    int64_t rows, A;
+    int cmax;
+    int rc = sarsa_layout_for(out, env, rows, A, cmax);
+    if (rc) return rc;
+    if (!sarsa_capacity_ok(capacity)) return fail(SE_EINVAL, "a sparse table's capacity must be a power of two >= 64");
+    int64_t entries, bytes;
+    if (__builtin_mul_overflow(capacity, A, &entries) || __builtin_mul_overflow(entries, (int64_t)12, &bytes))
+        return fail(SE_EINVAL, "the SARSA table's size overflows int64");
+    return sarsa_new(out, env, rows, A, cmax, entries, capacity);
 }
 
 int se_sarsa_layout(const se_sarsa* h, int64_t* rows, int32_t* A, int32_t* cmax) {
@@ -398,10 +688,32 @@ int se_sarsa_layout(const se_sarsa* h, int64_t* rows, int32_t* A, int32_t* cmax)
 int se_sarsa_bind(se_sarsa* h, double* q, const se_sarsa_state* st) {
     int rc = sarsa_ready(h, false);
     if (rc) return rc;
+    if (h->sparse) return fail(SE_EINVAL, "se_sarsa_bind on a sparse handle: call se_sarsa_bind_sparse");
     if (!q || !st) return fail(SE_EINVAL, "null argument");
     if (h->n > 0 && (!st->type || !st->a || !st->b || !st->fresh || !st->ep_len || !st->ep_return))
         return fail(SE_EINVAL, "null agent state buffer");
     h->q = q;
+    h->ag = *st;
+    h->bound = true;
+    return SE_OK;
+}
+
+int se_sarsa_bind_sparse(se_sarsa* h, int64_t* keys, double* pages, const se_sarsa_state* st) {
+    int rc = sarsa_ready(h, false);
+    if (rc) return rc;
+    if (!h->sparse) return fail(SE_EINVAL, "se_sarsa_bind_sparse on a dense handle: call se_sarsa_bind");
+    if (!keys || !pages || !st) return fail(SE_EINVAL, "null argument");
+    if (h->n > 0 && (!st->type || !st->a || !st->b || !st->fresh || !st->ep_len || !st->ep_return))
+        return fail(SE_EINVAL, "null agent state buffer");
+    if (h->n > 0) {  // used = the slots the caller's keys occupy (a preloaded table)
+        DeviceGuard g(h->device);
+        HIP_TRY(hipMemset(h->d_counters, 0, sizeof(unsigned long long)));
+        sarsa_count_kernel<<<grid_for(h->capacity), kBlock, 0, nullptr>>>(keys, h->capacity, h->d_counters);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(nullptr));
+    }
+    h->keys = keys;
+    h->pages = pages;
     h->ag = *st;
     h->bound = true;
     return SE_OK;
@@ -419,37 +731,12 @@ int se_sarsa_step(se_sarsa* h, double lr, double gamma, double epsilon, int32_t 
     if (env->n == 0) return SE_OK;
     if (!reward || !ended || !status || !fin_return || !fin_len) return fail(SE_EINVAL, "null output pointer");
     DeviceGuard g(env->device);
-    size_t lds;
-    rc = world_lds<sarsa_step_kernel>(env, lds);
-    if (rc) return rc;
-    SarsaArgs A{};
-    static_cast<EnvArgs&>(A) = env_args(env);
-    A.t = t;
-    A.ag = h->ag;
-    A.q = h->q;
-    A.owner = h->d_owner;
-    A.A = h->A;
-    A.cmax = h->cmax;
-    A.lr = lr;
-    A.gamma = gamma;
-    A.epsilon = epsilon;
-    A.learn = learn != 0;
-    A.max_steps = max_steps;
-    A.max_attempts = max_attempts;
-    A.park_entry = h->d_park_entry;
-    A.park_val = h->d_park_val;
-    A.reward = reward;
-    A.ended = ended;
-    A.status = status;
-    A.fin_return = fin_return;
-    A.fin_len = fin_len;
     const hipStream_t s = (hipStream_t)stream;
-    sarsa_step_kernel<<<grid_for(env->n), kBlock, lds, s>>>(A);
-    HIP_TRY(hipGetLastError());
-    if (A.learn) {
-        sarsa_commit_kernel<<<grid_for(env->n), kBlock, 0, s>>>(env->n, h->d_park_entry, h->d_park_val, h->q, h->d_owner);
-        HIP_TRY(hipGetLastError());
-    }
+    rc = h->sparse ? sarsa_launch_step(h, sarsa_sparse_table(h), h->pages, lr, gamma, epsilon, learn, max_steps,
+                                       max_attempts, t, reward, ended, status, fin_return, fin_len, s)
+                   : sarsa_launch_step(h, SarsaDense{h->q}, h->q, lr, gamma, epsilon, learn, max_steps, max_attempts,
+                                       t, reward, ended, status, fin_return, fin_len, s);
+    if (rc) return rc;
     env->step_t += 1;
     return SE_OK;
 }
@@ -462,21 +749,77 @@ int se_sarsa_choose(se_sarsa* h, double epsilon, uint32_t t, int32_t* type, int3
     if (env->n == 0) return SE_OK;
     if (!type || !a || !b) return fail(SE_EINVAL, "null output pointer");
     DeviceGuard g(env->device);
-    size_t lds;
-    rc = world_lds<sarsa_choose_kernel>(env, lds);
+    const hipStream_t s = (hipStream_t)stream;
+    return h->sparse ? sarsa_launch_choose(h, sarsa_sparse_table(h), epsilon, t, type, a, b, s)
+                     : sarsa_launch_choose(h, SarsaDense{h->q}, epsilon, t, type, a, b, s);
+}
+
+int se_sarsa_sparse_stats(se_sarsa* h, int64_t* capacity, int64_t* used, int64_t* dropped, void* stream) {
+    int rc = sarsa_ready(h, false);
     if (rc) return rc;
-    const SarsaChooseArgs A{env_args(env), t, h->q, h->A, h->cmax, epsilon, type, a, b};
-    sarsa_choose_kernel<<<grid_for(env->n), kBlock, lds, (hipStream_t)stream>>>(A);
-    HIP_TRY(hipGetLastError());
+    if (!h->sparse) return fail(SE_EINVAL, "se_sarsa_sparse_stats on a dense handle");
+    DeviceGuard g(h->device);
+    int64_t u, d;
+    rc = sarsa_counters(h, (hipStream_t)stream, u, d);
+    if (rc) return rc;
+    if (capacity) *capacity = h->capacity;
+    if (used) *used = u;
+    if (dropped) *dropped = d;
     return SE_OK;
+}
+
+int se_sarsa_sparse_grow(se_sarsa* h, int64_t* new_keys, double* new_pages, int64_t new_capacity, void* stream) {
+    int rc = sarsa_ready(h, true);
+    if (rc) return rc;
+    if (!h->sparse) return fail(SE_EINVAL, "se_sarsa_sparse_grow on a dense handle");
+    if (!new_keys || !new_pages) return fail(SE_EINVAL, "null argument");
+    if (!sarsa_capacity_ok(new_capacity)) return fail(SE_EINVAL, "a sparse table's capacity must be a power of two >= 64");
+    int64_t entries, bytes;
+    if (__builtin_mul_overflow(new_capacity, (int64_t)h->A, &entries) || __builtin_mul_overflow(entries, (int64_t)12, &bytes))
+        return fail(SE_EINVAL, "the SARSA table's size overflows int64");
+    DeviceGuard g(h->device);
+    const hipStream_t s = (hipStream_t)stream;
+    int64_t used, dropped;
+    rc = sarsa_counters(h, s, used, dropped);  // the steps queued before have run
+    if (rc) return rc;
+    if (new_capacity < used)
+        return fail(SE_EINVAL, "the table holds " + std::to_string(used) + " rows, more than the new capacity");
+    if (h->n > 0) {
+        uint32_t* owner = nullptr;
+        hipError_t e = hipMalloc(&owner, (size_t)entries * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemsetAsync(owner, 0xff, (size_t)entries * sizeof(uint32_t), s);
+        if (e == hipSuccess) {
+            sarsa_grow_kernel<<<grid_for(h->capacity), kBlock, 0, s>>>(h->keys, h->pages, h->capacity, new_keys,
+                                                                       new_pages, new_capacity - 1, h->A);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            (void)device_free({owner});
+            return fail(SE_EHIP, std::string("se_sarsa_sparse_grow: ") + hipGetErrorString(e));
+        }
+        HIP_TRY(device_free({h->d_owner}));
+        h->d_owner = owner;
+    }
+    h->keys = new_keys;
+    h->pages = new_pages;
+    h->capacity = new_capacity;
+    return SE_OK;
+}
+
+int64_t se_sarsa_sparse_home(int64_t row, int64_t capacity) {
+    if (row < 0 || !sarsa_capacity_ok(capacity)) return -1;
+    return (int64_t)(sarsa_mix((uint64_t)row) & (uint64_t)(capacity - 1));
 }
 
 int se_sarsa_destroy(se_sarsa* h) {
     if (!h) return SE_OK;
     DeviceGuard g(h->device);
-    const hipError_t e = device_free({h->d_owner, h->d_park_entry, h->d_park_val});
+    const hipError_t e = device_free({h->d_owner, h->d_park_entry, h->d_park_val, h->d_park_slot, h->d_counters});
     delete h;
     return e == hipSuccess ? SE_OK : fail(SE_EHIP, std::string("hipFree: ") + hipGetErrorString(e));
 }
 
 }  // extern "C"
+

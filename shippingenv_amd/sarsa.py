@@ -1,6 +1,7 @@
 """VecSARSAAgent: the reference's SARSAAgent (agents/sarsa.py) for the N envs of a VecEnv.
 
-One learner owns one dense f64 Q-table in device memory; every se_sarsa_step runs the body of
+One learner owns one f64 Q-table in device memory, dense (every row of the layout) or sparse (a
+hash table of the rows met, for worlds whose dense table does not fit); every se_sarsa_step runs the body of
 train's inner loop (:255-272) for all envs at once: _try_action on the pending action,
 choose_action on the new state, the update, and the restart of finished episodes. All envs
 read the table as the previous vector step left it; where several update one entry in a step,
@@ -12,6 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -26,6 +28,50 @@ MOVES = ((0, -1), (0, 1), (-1, 0), (1, 0))  # _get_possible_actions' order (:105
 BUCKETS = ((0, 0), (1, 0), (2, 1), (3, 1), (4, 2), (4, 3), (4, 4))
 
 
+def sparse_home(rows, capacity):
+    """The sparse table's home buckets of an int64 array of rows (include/shipenv.h: the
+    splitmix64 finaliser masked to the capacity), as se_sarsa_sparse_home gives them one by one."""
+    z = np.asarray(rows, np.int64).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        z ^= z >> np.uint64(30)
+        z *= np.uint64(0xBF58476D1CE4E5B9)
+        z ^= z >> np.uint64(27)
+        z *= np.uint64(0x94D049BB133111EB)
+        z ^= z >> np.uint64(31)
+    return (z & np.uint64(capacity - 1)).astype(np.int64)
+
+
+def sparse_image(rows, pages, capacity):
+    """(keys int64[capacity], pages f64[capacity, A]) on the host holding the distinct `rows` with
+    their `pages`: every row in the first empty slot of its probe."""
+    rows = np.asarray(rows, np.int64)
+    pages = np.asarray(pages, np.float64).reshape(len(rows), -1)
+    if len(rows) > capacity:
+        raise ValueError(f"{len(rows)} rows do not fit a sparse table of capacity {capacity}")
+    keys = np.full(capacity, -1, np.int64)
+    out = np.zeros((capacity, pages.shape[1]), np.float64)
+    pos, todo = sparse_home(rows, capacity), np.arange(len(rows))
+    while todo.size:
+        at = pos[todo]
+        free = keys[at] < 0
+        slots, first = np.unique(at[free], return_index=True)  # one taker per empty slot
+        took = todo[free][first]
+        keys[slots] = rows[took]
+        out[slots] = pages[took]
+        placed = np.zeros(len(rows), bool)
+        placed[took] = True
+        todo = todo[~placed[todo]]
+        pos[todo] = (pos[todo] + 1) & (capacity - 1)
+    return keys, out
+
+
+def _pow2_at_least(v):
+    c = 64
+    while c < v:
+        c *= 2
+    return c
+
+
 class VecSARSAAgent:
     """SARSAAgent(env, learning_rate, discount_factor, epsilon, epsilon_min, epsilon_decay) with
     the reference's defaults (utils/constants.py:40-46). max_steps restarts an episode after
@@ -33,12 +79,26 @@ class VecSARSAAgent:
     max_attempts (1..64) bounds _try_action's unbounded retry, a step it cuts has status CUT.
     max_table_bytes refuses a table (with its claim words, 12 bytes per entry) beyond it.
 
+    table="sparse" keeps a hash table of rows instead (include/shipenv.h): keys int64[capacity] and
+    pages f64[capacity, A], a page per state some update met, `capacity` a power of two >= 64 (the
+    default: the smallest one >= max(64, 4 n)); max_table_bytes then bounds capacity * (A * 12 + 8).
+    It computes what the dense table does, bit for bit, in worlds of any port count. train grows it;
+    a caller who steps it by hand calls reserve() or watches stats() and calls grow(): an update
+    that finds the table full is dropped and counted in stats()["dropped"].
+
     The envs must have been reset (env.reset()) or loaded before the first step; every env starts
     fresh, that is, its first step chooses its action first. q is the table, a torch f64 tensor
-    [rows, A] in the layout of include/shipenv.h; t, the vector-step number, selects the draws."""
+    [rows, A] in the layout of include/shipenv.h (sparse: keys and pages); t, the vector-step
+    number, selects the draws."""
 
     def __init__(self, env, learning_rate=0.1, discount_factor=0.9, epsilon=1.0, epsilon_min=0.0001,
-                 epsilon_decay=0.999, max_steps=1000, max_attempts=8, max_table_bytes=None):
+                 epsilon_decay=0.999, max_steps=1000, max_attempts=8, max_table_bytes=None, table="dense",
+                 capacity=None):
+        if table not in ("dense", "sparse"):
+            raise ValueError(f"table must be 'dense' or 'sparse', not {table!r}")
+        if table == "dense" and capacity is not None:
+            raise ValueError("capacity belongs to table='sparse'")
+        self.table = table
         self.env = env
         self.lr, self.gamma = float(learning_rate), float(discount_factor)
         self.epsilon, self.epsilon_min, self.epsilon_decay = float(epsilon), float(epsilon_min), float(epsilon_decay)
@@ -47,13 +107,25 @@ class VecSARSAAgent:
         self._carry = 0  # finished episodes not yet paid for with a decay (train)
         self._h = C.c_void_p()
         limit = (1 << 63) - 1 if max_table_bytes is None else int(max_table_bytes)
+        self._limit = limit
+        dev, n = env.device, env.n
+        if table == "sparse":
+            self.capacity = _pow2_at_least(max(64, 4 * n)) if capacity is None else int(capacity)
+            # A = P + 4 + cmax + 20 (include/shipenv.h), known before the handle allocates its claim words
+            self._refuse_beyond_limit(self.capacity, env.P + 24 + max([20] + [int(c) for c in env.port_cargo]))
         with torch.cuda.device(env.device):
-            N.check(N.lib().se_sarsa_create(C.byref(self._h), env._h, limit))
+            if table == "sparse":
+                N.check(N.lib().se_sarsa_create_sparse(C.byref(self._h), env._h, self.capacity))
+            else:
+                N.check(N.lib().se_sarsa_create(C.byref(self._h), env._h, limit))
         rows, A, cmax = C.c_int64(), C.c_int32(), C.c_int32()
         N.check(N.lib().se_sarsa_layout(self._h, C.byref(rows), C.byref(A), C.byref(cmax)))
         self.rows, self.A, self.cmax = rows.value, A.value, cmax.value
-        dev, n = env.device, env.n
-        self.q = torch.zeros((self.rows, self.A), dtype=torch.float64, device=dev)
+        if table == "sparse":
+            assert self.A == env.P + 24 + max([20] + [int(c) for c in env.port_cargo]), "A is not the header's"
+            self.keys, self.pages = self._empty(self.capacity)
+        else:
+            self.q = torch.zeros((self.rows, self.A), dtype=torch.float64, device=dev)
         self.type, self.a, self.b = (torch.zeros(n, dtype=torch.int32, device=dev) for _ in range(3))
         self.fresh = torch.ones(n, dtype=torch.uint8, device=dev)
         self.ep_len = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -68,7 +140,94 @@ class VecSARSAAgent:
     def _bind(self):
         self._state = N.SeSarsaState(*[t.data_ptr() for t in (self.type, self.a, self.b, self.fresh, self.ep_len,
                                                               self.ep_return)])
-        N.check(N.lib().se_sarsa_bind(self._h, _ptr(self.q), C.byref(self._state)))
+        if self.table == "sparse":
+            torch.cuda.synchronize(self.env.device)  # the bind counts the keys: whatever wrote them has finished
+            with torch.cuda.device(self.env.device):
+                N.check(N.lib().se_sarsa_bind_sparse(self._h, _ptr(self.keys), _ptr(self.pages), C.byref(self._state)))
+        else:
+            N.check(N.lib().se_sarsa_bind(self._h, _ptr(self.q), C.byref(self._state)))
+
+    # ------------------------------------------------------------------ the sparse table
+    def _sparse_only(self, what):
+        if self.table != "sparse":
+            raise ValueError(f"{what} belongs to table='sparse'")
+
+    def _refuse_beyond_limit(self, capacity, A=None):
+        need = capacity * ((self.A if A is None else A) * 12 + 8)
+        if need > self._limit:
+            raise ValueError(f"a sparse SARSA table of capacity {capacity} with its claim words needs {need} bytes, "
+                             f"more than max_table_bytes ({self._limit})")
+
+    def _empty(self, capacity):
+        dev = self.env.device
+        return (torch.full((capacity,), -1, dtype=torch.int64, device=dev),
+                torch.zeros((capacity, self.A), dtype=torch.float64, device=dev))
+
+    def stats(self):
+        """The table's size: dense {"table", "rows", "bytes"}; sparse {"table", "capacity", "used",
+        "dropped", "bytes"}: the pages taken and the updates lost to a full table since the agent was
+        made (0 unless the table was stepped when full), after a synchronisation of the stream. bytes
+        counts the table and the claim words."""
+        if self.table != "sparse":
+            return {"table": "dense", "rows": self.rows, "bytes": self.rows * self.A * 12}
+        cap, used, dropped = C.c_int64(), C.c_int64(), C.c_int64()
+        N.check(N.lib().se_sarsa_sparse_stats(self._h, C.byref(cap), C.byref(used), C.byref(dropped), self.env._stream()))
+        return {"table": "sparse", "capacity": cap.value, "used": used.value, "dropped": dropped.value,
+                "bytes": cap.value * (self.A * 12 + 8)}
+
+    def grow(self, capacity=None):
+        """Move the sparse table into new buffers of `capacity` slots (the default: twice as many);
+        keys and pages are new tensors afterwards, the old ones are left as they were."""
+        self._sparse_only("grow")
+        capacity = 2 * self.capacity if capacity is None else int(capacity)
+        self._refuse_beyond_limit(capacity)
+        if capacity < 64 or capacity & (capacity - 1):
+            raise ValueError("a sparse table's capacity must be a power of two >= 64")
+        keys, pages = self._empty(capacity)
+        with torch.cuda.device(self.env.device):
+            N.check(N.lib().se_sarsa_sparse_grow(self._h, _ptr(keys), _ptr(pages), capacity, self.env._stream()))
+        self.keys, self.pages, self.capacity = keys, pages, capacity
+
+    def reserve(self, new_rows):
+        """Grow (doubling) until the table has room for new_rows more rows (never more than the
+        layout has) and is at most half full: what train does before every run of steps, for a
+        caller who steps by hand (k steps add at most k * n rows). One synchronisation."""
+        self._sparse_only("reserve")
+        used = self.stats()["used"]
+        want = min(self.rows, used + new_rows)
+        capacity = self.capacity
+        while capacity < want or 2 * used > capacity:
+            capacity *= 2
+        if capacity != self.capacity:
+            self.grow(capacity)
+
+    def _rows_and_pages(self):
+        """The occupied slots on the host: (rows int64[m], pages f64[m, A])."""
+        keys = self.keys.cpu()
+        occ = torch.nonzero(keys >= 0).view(-1)
+        return keys[occ].numpy(), self.pages[occ.to(self.pages.device)].cpu().numpy()
+
+    def _install(self, rows, pages):
+        """Replace the sparse table by the given rows, through the host."""
+        need = _pow2_at_least(2 * len(rows))
+        if need > self.capacity:
+            self.grow(need)
+        keys, out = sparse_image(rows, pages, self.capacity)
+        self.keys.copy_(torch.from_numpy(keys))
+        self.pages.copy_(torch.from_numpy(out))
+        self._bind()  # counts the rows
+
+    def to_dense(self):
+        """The table as the dense [rows, A] tensor (dense: q itself); refused beyond max_table_bytes."""
+        if self.table != "sparse":
+            return self.q
+        need = self.rows * self.A * 8
+        if need > self._limit:
+            raise ValueError(f"the dense SARSA table needs {need} bytes, more than max_table_bytes ({self._limit})")
+        q = torch.zeros((self.rows, self.A), dtype=torch.float64, device=self.env.device)
+        occ = torch.nonzero(self.keys >= 0).view(-1)
+        q[self.keys[occ]] = self.pages[occ]
+        return q
 
     # ------------------------------------------------------------------ stepping
     def step(self, learn=True, epsilon=None):
@@ -109,7 +268,12 @@ class VecSARSAAgent:
         episodes side by side, so epsilon decays once per n finished episodes, counted from
         `ended` every sync_every steps (one host synchronisation each) with the remainder
         carried: each env's episodes see the reference's schedule on average. This pacing is
-        ours; the reference has no counterpart for it."""
+        ours; the reference has no counterpart for it.
+
+        The sparse table is grown at the same synchronisations: before every run of k steps until
+        it has room for the k * n rows those steps can add at most (never more than the layout's
+        rows) and is no more than half full, so that no update is dropped; a table that max_table_bytes
+        does not let grow that far raises (a smaller sync_every needs less room)."""
         n = max(self.env.n, 1)
         count = torch.zeros((), dtype=torch.int64, device=self.env.device)
         total = torch.zeros((), dtype=torch.float64, device=self.env.device)
@@ -118,6 +282,8 @@ class VecSARSAAgent:
             k = min(int(sync_every), steps - done_steps)
             count.zero_()
             total.zero_()
+            if self.table == "sparse":
+                self.reserve(k * self.env.n)
             for _ in range(k):
                 _, ended, _ = self.step(learn=True)
                 count += ended.sum()
@@ -130,6 +296,8 @@ class VecSARSAAgent:
             while self._carry >= n:
                 self._carry -= n
                 self.decay_epsilon()
+        if self.table == "sparse":
+            self.reserve(0)
         return episodes, ret
 
     def test_policy(self, steps):
@@ -176,21 +344,43 @@ class VecSARSAAgent:
 
     def q_items(self):
         """The non-zero entries as {reference dict key: value}."""
+        if self.table == "sparse":
+            rows, pages = self._rows_and_pages()
+            s, k = np.nonzero(pages)
+            return {self.entry_key(e): v for e, v in zip((rows[s] * self.A + k).tolist(), pages[s, k].tolist())}
         flat = self.q.view(-1)
         idx = torch.nonzero(flat, as_tuple=False).view(-1)
         vals = flat[idx].cpu().tolist()
         return {self.entry_key(e): v for e, v in zip(idx.cpu().tolist(), vals)}
 
     def save(self, path):
-        torch.save({"q": self.q.cpu(), "epsilon": self.epsilon, "lr": self.lr, "gamma": self.gamma,
-                    "layout": (self.rows, self.A, self.cmax)}, path)
+        doc = {"epsilon": self.epsilon, "lr": self.lr, "gamma": self.gamma, "layout": (self.rows, self.A, self.cmax),
+               "table": self.table}
+        if self.table == "sparse":  # the rows held and their pages: where they lay is not part of the table
+            rows, pages = self._rows_and_pages()
+            doc["rows"], doc["pages"] = torch.from_numpy(rows), torch.from_numpy(pages)
+        else:
+            doc["q"] = self.q.cpu()
+        torch.save(doc, path)
 
     def load(self, path):
         data = torch.load(path, map_location="cpu")
         if tuple(data["layout"]) != (self.rows, self.A, self.cmax):
             raise ValueError(f"the saved table's layout {tuple(data['layout'])} is not this world's "
                              f"{(self.rows, self.A, self.cmax)}")
-        self.q.copy_(data["q"])
+        saved_sparse = data.get("table", "dense") == "sparse"  # a checkpoint of either kind loads into either
+        if self.table == "sparse":
+            if saved_sparse:
+                rows, pages = data["rows"], data["pages"]
+            else:  # the rows with a non-zero entry
+                rows = torch.nonzero((data["q"] != 0).any(1)).view(-1)
+                pages = data["q"][rows]
+            self._install(rows.numpy(), pages.numpy())
+        elif saved_sparse:
+            self.q.zero_()
+            self.q[data["rows"].to(self.q.device)] = data["pages"].to(self.q.device)
+        else:
+            self.q.copy_(data["q"])
         self.epsilon = data.get("epsilon", self.epsilon_min)  # :402-404
         self.lr = data.get("lr", self.lr)
         self.gamma = data.get("gamma", self.gamma)
