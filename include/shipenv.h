@@ -677,6 +677,72 @@ int se_sarsa_sparse_grow(se_sarsa* s, int64_t* new_keys, double* new_pages, int6
  * row or a capacity that is not a power of two >= 64. */
 int64_t se_sarsa_sparse_home(int64_t row, int64_t capacity);
 
+/* Table-policy rollouts (an extension: the reference has no rollout of its SARSA policy; what it
+ * has is restated exactly: choose_action, _try_action's fallback and test_policy's loop): what
+ * env src[r] earns if it plays the bound Q-table, dense or sparse, from where it stands, without
+ * playing it. Rollout r copies env src[r] (the env's state and counters are only read) and plays
+ * positions k = 0 .. steps - 1 on the private ship s under the key (seed, ids ? ids[r] :
+ * rollout_base + r). Each lane carries one flag, fallback, clear at position 0. The position:
+ *   1. d = the block (k, slot 12), the block every rollout kind draws at position k: word 0 the
+ *      sample_action word, words 1-3 u_fuel, u_gate, u_type.
+ *   2. The action. With fallback set it is sample_action(s, d[0]). Else, if epsilon > 0, one
+ *      block is drawn at (k, slot 22) and the position explores iff word0 * 2^-32 < epsilon (the
+ *      strict test of random.random() < self.epsilon), the explored action being
+ *      sample_action(s, d[0]); with epsilon == 0 slot 22 is not drawn at all. Otherwise the
+ *      action is greedy, se_sarsa_choose's choice with epsilon = 0 on the row of the private
+ *      ship's discretised state: the first strict maximum from -inf in _get_possible_actions'
+ *      order, an absent sparse row answering SELECT 0, and where nothing compares greater (NaN,
+ *      -inf) sample_action(s, d[0]).
+ *   3. A sample_action that raises (a negative SE_SAMPLE_* type) ends the rollout as se_rollout's
+ *      does: status SE_PLAN_STUCK, stuck_at = k, sample_type the type; the step's words are unused.
+ *   4. Otherwise the action is stepped with d's words 1-3 and, for a partial loss or an arrival,
+ *      the block (k, slot 13), as se_rollout_plan steps position k. A raising step leaves the ship
+ *      untouched and counts in end.raised (the first one's error and position are kept); a counted
+ *      step adds its f64 reward to ret[r] in order and 1 to counted[r]; one that reports done
+ *      ends the rollout with SE_PLAN_DONE.
+ *   5. fallback is _try_action (agents/sarsa.py:201-220) with the positions as its attempts: a
+ *      raising step sets it, a counted step clears it. Without it a greedy choice that raises
+ *      would raise at every later position, since nothing it reads has changed.
+ *   6. Running out of positions is SE_PLAN_END. steps = 0 writes ret 0, counted 0 and
+ *      SE_PLAN_END; a bad src[r] writes SE_PLAN_BAD_SRC with the zeros and -1 se_rollout_plan
+ *      writes. stuck_at is -1 and sample_type 0 for a rollout that is not stuck.
+ * What follows: with epsilon = 1 (every position samples with word 0 of slot 12) the rollout
+ * equals se_rollout of the same rollout_base with max_steps = max_attempts = steps, in ret (bits),
+ * counted steps and the end ship, DONE as DONE, MAX_STEPS / ATTEMPTS as END, RAISED as STUCK; for
+ * any epsilon it equals se_rollout_plan (typed) under the same ids fed the actions it emitted, in
+ * ret (bits), counted, raised, first_err, first_err_at, the end ship and DONE / END (a stuck
+ * rollout up to stuck_at); the first action at epsilon = 0 is se_sarsa_choose(epsilon = 0)'s for
+ * that env (where nothing compares greater both sample, each with its own word: slot 12's here,
+ * slot 20's there); and a sparse and a dense table holding the same map give the same bytes.
+ *
+ * Buffers (device): src, m entries, and ids, m entries or NULL, are only read; ret, counted and
+ * status, m entries each, are written whole; of `out` (NULL: nothing more is wanted) every
+ * pointer that is not NULL gets m entries (stuck_at, sample_type and the nine of `end`), and
+ * act_type, act_a and act_b, all three or none, get elements 0 .. m - 1 of each of their `steps`
+ * rows of stride ld (step-major, element k * ld + r, as se_rollout_plan reads them: the action of
+ * position k, and type 0, a 0, b 0 for a position not played, a stuck position and a bad
+ * source); the ld - m columns behind a row are neither read nor written. A NULL pointer's output
+ * is not computed. The call reads the env's bound state and the table and writes none of it: not a
+ * byte of the env's state and counters, of q or of keys and pages, of the se_sarsa_state fields,
+ * of the handle's claim words and park buffers; it launches neither the claim nor the commit
+ * kernel, and neither the env's nor the learner's step number moves.
+ * Misuse (m, steps or rollout_base negative; epsilon NaN or negative; a null src, ret, counted
+ * or status with m > 0; some but not all of act_type, act_a, act_b; with them ld < m, an array
+ * that is not 16-byte aligned or, for steps > 1, ld not a multiple of 4) is SE_EINVAL before any
+ * launch, whatever the handle's state, and writes nothing. Then the handle is held to
+ * se_sarsa_step's readiness: not bound, or se_set_ports since create, is SE_ESTATE. m = 0 is a
+ * no-op. One launch, no allocation, no synchronisation: capturable. */
+typedef struct se_table_out {      /* every pointer may be NULL: not wanted */
+    int32_t *stuck_at, *sample_type;            /* m entries */
+    int32_t *act_type, *act_a, *act_b;          /* step-major [steps][ld] rows as se_rollout_plan reads them;
+                                                   positions not played hold type 0, a 0, b 0 */
+    int64_t ld;                                  /* row stride of the act_* arrays, >= m, rows 16-byte aligned */
+    se_plan_out end;
+} se_table_out;
+int se_rollout_sarsa(se_sarsa* s, double epsilon, const int32_t* src, int64_t m, const int64_t* ids,
+                     int64_t rollout_base, int32_t steps, double* ret, int32_t* counted, int32_t* status,
+                     const se_table_out* out, void* stream);
+
 /* DQN policy step fused on the GPU (agents/dqn.py): DQNNetwork 6+4P -> 128 -> 128 -> A
  * (A = 4+P+250, :21-33) evaluated with bf16 MFMA and f32 accumulation on the
  * observation preprocess_state builds (utils/preprocessing.py:25-62; its constant port

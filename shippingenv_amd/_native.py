@@ -76,6 +76,12 @@ class SeNavOut(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("arrivals", "nav_status", "stuck_at")] + [("end", SePlanOut)]
 
 
+class SeTableOut(C.Structure):
+    """se_table_out: what se_rollout_sarsa writes beside ret, counted and status (NULL: not wanted)."""
+    _fields_ = ([(name, C.c_void_p) for name in ("stuck_at", "sample_type", "act_type", "act_a", "act_b")] +
+                [("ld", C.c_int64), ("end", SePlanOut)])
+
+
 class SeDoneRec(C.Structure):
     _fields_ = [("env", C.c_int32), ("ep_return", C.c_float), ("ep_len", C.c_int32),
                 ("step", C.c_int32)]
@@ -127,6 +133,7 @@ SIGNATURES = {
     "se_sarsa_sparse_stats": [_P, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _P],
     "se_sarsa_sparse_grow": [_P, _P, _P, _i64, _P],
     "se_sarsa_sparse_home": [_i64, _i64],
+    "se_rollout_sarsa": [_P, C.c_double, _P, _i64, _P, _i64, _i32, _P, _P, _P, C.POINTER(SeTableOut), _P],
     "se_qnet_create": [C.POINTER(_P), _P],
     "se_qnet_set_weights": [_P, _P, _P, _P, _P, _P, _P, _P],
     "se_policy": [_P, _P, C.c_double, _u32, _P, _i64, _P],

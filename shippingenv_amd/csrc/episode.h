@@ -1,8 +1,9 @@
 #pragma once
 // episode.h — what a rollout of numbered positions on a private ship is, whatever chooses its
 // actions: EpisodeArgs, the lane (episode_lane), the tally (EpisodeTally) and the store of the
-// results (episode_store). plan.h's scripted rollouts and nav.h's navigated rollouts are this
-// scaffold around their own step loops; a new rollout kind plugs in the same way.
+// results (episode_store). plan.h's scripted rollouts, nav.h's navigated rollouts and
+// sarsa_rollout.h's table rollouts are this scaffold around their own step loops; a new rollout
+// kind plugs in the same way.
 //
 // A fragment of shipenv.hip's translation unit, included inside its anonymous
 // namespace after rollout.h: not a stand-alone header.

@@ -42,6 +42,8 @@ enum Slot : uint32_t {
     kSlotSarsa = 20,         // se_sarsa_step, per env, t = the vector step: explore uniform and sample word of
                              // next_action (words 0, 1) and of a fresh env's first choice (words 2, 3)
     kSlotSarsaReset = 21,    // se_sarsa_step's restart: words 0 origin, 1 dest (as kSlotExplicitReset)
+    kSlotRolloutQ = 22,      // se_rollout_sarsa, per rollout, t = the position: word 0 the explore uniform (drawn
+                             // only with epsilon > 0 and outside _try_action's fallback)
     kSlotSarsaTry = 32,      // _try_action attempt j at 32 + 2j: sample word (j >= 1), u_fuel, u_gate, u_type;
                              // 33 + 2j (partial loss / arrival): 3 beta uniforms, dest; j < 64, up to slot 159
 };

@@ -936,6 +936,7 @@ int se_host_destroy(se_host* h) {
 #include "nav.h"   // before mcts.h: se_mcts_choose_nav plays the navigator
 #include "mcts.h"
 #include "sarsa.h"
+#include "sarsa_rollout.h"  // after sarsa.h: plays its tables through sarsa_choose
 #include "replay.h"
 #include "qtrain.h"
 #include "server.h"

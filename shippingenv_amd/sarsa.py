@@ -12,6 +12,7 @@ Nothing here falls back to the host: a missing kernel is an error.
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -26,6 +27,28 @@ MOVE, SELECT, TAKE_FUEL, TAKE_CARGO = 1, 2, 3, 4
 MOVES = ((0, -1), (0, 1), (-1, 0), (1, 0))  # _get_possible_actions' order (:105-110)
 # fuel class -> (cargo_bucket, fuel_bucket) of discretize_state, both read from the fuel
 BUCKETS = ((0, 0), (1, 0), (2, 1), (3, 1), (4, 2), (4, 3), (4, 4))
+
+
+class TableRollout(NamedTuple):
+    """What VecSARSAAgent.rollout returns: device tensors of m entries (the ship's six are None
+    without return_end, the action rows None without return_actions)."""
+    ret: torch.Tensor           # f64: the counted steps' rewards summed in order
+    counted: torch.Tensor       # counted steps
+    status: torch.Tensor        # PLAN_DONE / PLAN_END / PLAN_BAD_SRC / PLAN_STUCK
+    stuck_at: torch.Tensor      # the position whose sample_action raised, -1 if none did
+    sample_type: torch.Tensor   # its SAMPLE_* type (status PLAN_STUCK), else 0
+    raised: torch.Tensor        # raising steps
+    first_err: torch.Tensor     # ERR_* of the first raising step, 0 if none
+    first_err_at: torch.Tensor  # its position, -1 if none
+    x: Optional[torch.Tensor] = None
+    y: Optional[torch.Tensor] = None
+    fuel: Optional[torch.Tensor] = None
+    cargo: Optional[torch.Tensor] = None
+    origin: Optional[torch.Tensor] = None
+    dest: Optional[torch.Tensor] = None
+    act_type: Optional[torch.Tensor] = None  # [steps, m] views of rows rollout_plan takes as they
+    act_a: Optional[torch.Tensor] = None     # are: the action of every position played, type 0
+    act_b: Optional[torch.Tensor] = None     # behind the end
 
 
 def sparse_home(rows, capacity):
@@ -303,7 +326,8 @@ class VecSARSAAgent:
     def test_policy(self, steps):
         """Greedy evaluation (test_policy :315-356: deterministic choices, no update) for `steps`
         vector steps from fresh resets -> {start port: mean return of the episodes that finished}.
-        The learner's step number t advances; the table does not change."""
+        The learner's step number t advances; the table does not change.
+        evaluate() values the table from the envs' current states without touching them or t."""
         env = self.env
         self.restart()
         P = env.P
@@ -319,6 +343,56 @@ class VecSARSAAgent:
             start = torch.where(fin, env.origin.to(torch.int64), start)
         s, c = sums.cpu().tolist(), cnts.cpu().tolist()
         self.restart()
+        return {p: s[p] / c[p] for p in range(P) if c[p] > 0}
+
+    # ------------------------------------------------------------------ rollouts
+    def rollout(self, src=None, steps=100, epsilon=0.0, ids=None, rollout_base=0, return_end=False,
+                return_actions=False):
+        """Table-policy rollouts (se_rollout_sarsa): rollout r plays the table, greedy or
+        epsilon-greedy, for `steps` positions on a private copy of env src[r] (int32 [m]; None:
+        every env once). The envs, their counters, the table, the learner state and t are
+        untouched. ids (int64 [m]) names each rollout's Philox stream instead of rollout_base + r.
+        A step that raises makes the next position sample its action, as _try_action does; a
+        sample_action that raises ends the rollout (PLAN_STUCK). Position k draws what
+        rollout_plan's position k draws: the rollout equals rollout_plan of the actions it
+        emitted (return_actions), and with epsilon = 1 env.rollout of the same base. Returns a
+        TableRollout of fresh tensors."""
+        env = self.env
+        if src is None:
+            src = torch.arange(env.n, dtype=torch.int32, device=env.device)
+        elif not isinstance(src, torch.Tensor):
+            src = torch.as_tensor(np.asarray(src))
+        m, steps = src.numel(), int(steps)
+        s = env._dev(src, torch.int32, count=m)
+        idt = None if ids is None else env._dev(ids, torch.int64, count=m)
+        # own: stuck_at, sample_type
+        ret, (counted, status), own, noted, end, plan_out = env._episode_outputs(m, return_end, extra=2)
+        acts, ld = (None, None, None), (m + 3) & ~3  # rows 16-byte aligned
+        if return_actions:
+            acts = tuple(torch.empty((max(steps, 0), ld), dtype=torch.int32, device=env.device) for _ in range(3))
+        out = N.SeTableOut(*[t.data_ptr() for t in own], *[None if t is None else t.data_ptr() for t in acts], ld,
+                           plan_out)
+        N.check(N.lib().se_rollout_sarsa(self._h, float(epsilon), _ptr(s), m, _ptr(idt), int(rollout_base), steps,
+                                         _ptr(ret), _ptr(counted), _ptr(status), C.byref(out), env._stream()))
+        self._keep = (s, idt)
+        return TableRollout(ret, counted, status, *own, *noted, *end, *[None if t is None else t[:, :m] for t in acts])
+
+    def evaluate(self, steps=100, ids=None, rollout_base=0):
+        """What the table is worth from where the envs stand -> {start port: mean ret of the greedy
+        (epsilon = 0) rollouts of `steps` positions from the envs whose current origin is that
+        port}; envs without an origin are left out. One launch, the means on the device and one
+        host read; the envs, t and the table are untouched, so it may run in the middle of
+        training, and under the same ids it is comparable draw for draw with
+        VecNavigator.rollout and, at epsilon = 1, env.rollout."""
+        env, P = self.env, self.env.P
+        ret = self.rollout(None, steps, 0.0, ids, rollout_base).ret
+        origin = env.origin.to(torch.int64)
+        has = (origin >= 0) & (origin < P)  # SE_NONE (255) names no port
+        idx = torch.where(has, origin, torch.zeros_like(origin))
+        acc = torch.zeros((2, P), dtype=torch.float64, device=env.device)
+        acc[0].index_add_(0, idx, torch.where(has, ret, torch.zeros_like(ret)))
+        acc[1].index_add_(0, idx, has.to(torch.float64))
+        s, c = acc.cpu().tolist()
         return {p: s[p] / c[p] for p in range(P) if c[p] > 0}
 
     # ------------------------------------------------------------------ the table
