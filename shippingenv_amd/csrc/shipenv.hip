@@ -116,6 +116,7 @@ struct se_env {
     bool seq_gate_pool = true;  // the fused launch draws GATE through the wave's pool (SHIPENV_SEQ_GATE_POOL=0: draw2)
     bool seq_ring = true;       // the fused launch's regular waves step on the bordered cell table (SHIPENV_SEQ_RING=0: none do)
     bool seq_screen = true;     // the GATE pool's refill screens its words, cold steps test no gate (SHIPENV_SEQ_SCREEN=0: every step does)
+    bool ports_distinct = false;  // all ports lie on distinct cells (build_world_image): with two or more, the fused launch may test arrivals by the cell code
 };
 
 // A host-resident world (se_host_*): no device, no HIP call. It steps envs whose SoA
@@ -221,10 +222,11 @@ bool mask_tiled() {
 }
 
 // The world image (layout above WorldDims, world.h) of an H x W map and P ports, built on the
-// host: uploaded by se_create / se_set_ports, kept as is by the host handles.
+// host: uploaded by se_create / se_set_ports, kept as is by the host handles. *distinct: do all
+// ports lie on distinct cells, so that a cell's code names the one port on it (step_lean.h).
 int build_world_image(int H, int W, const std::vector<uint8_t>& water, int32_t P, const int32_t* px,
                       const int32_t* py, const int32_t* pf, const int32_t* pc, WorldDims& dims,
-                      std::vector<uint32_t>& img) {
+                      std::vector<uint32_t>& img, bool* distinct = nullptr) {
     if (P < 0 || P > SE_MAX_PORTS) return fail(SE_EINVAL, "P must be in [0, 254]");
     for (int i = 0; i < P; ++i) {
         if (px[i] < 0 || px[i] >= H || py[i] < 0 || py[i] >= W)
@@ -274,6 +276,7 @@ int build_world_image(int H, int W, const std::vector<uint8_t>& water, int32_t P
     rtab[9] = 0.0;
     memcpy(&img[d.rtab()], rtab, sizeof rtab);
     dims = d;
+    if (distinct) *distinct = ports_on_distinct_cells(P, px, py);
     return SE_OK;
 }
 
@@ -281,7 +284,8 @@ int upload_world(se_env* env, int32_t P, const int32_t* px, const int32_t* py, c
                  const int32_t* pc) {
     WorldDims d{};
     std::vector<uint32_t> img;
-    int rc = build_world_image(env->dims.H, env->dims.W, env->water, P, px, py, pf, pc, d, img);
+    bool distinct = false;
+    int rc = build_world_image(env->dims.H, env->dims.W, env->water, P, px, py, pf, pc, d, img, &distinct);
     if (rc) return rc;
     // the bordered cell table of the fused step sequence's regular waves (step_lean.h) follows
     // the image; no other kernel reads past the image
@@ -292,6 +296,7 @@ int upload_world(se_env* env, int32_t P, const int32_t* px, const int32_t* py, c
     HIP_TRY(hipMemcpy(env->d_world, img.data(), (size_t)d.padded() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(env->d_world + d.padded(), ring.data(), ring.size(), hipMemcpyHostToDevice));
     env->dims = d;
+    env->ports_distinct = distinct;
     env->port_x.assign(px, px + P);
     env->port_y.assign(py, py + P);
     env->cmax = env->fmax = env->stock_cargo_max = 0;
@@ -432,7 +437,7 @@ int launch_step_seq(se_env* env, const int32_t* act, int64_t ld, int32_t steps, 
         const size_t lds = without + ring;
         const auto kernel = pool ? (env->nt_loads ? step_seq_kernel<true, true> : step_seq_kernel<false, true>)
                                  : (env->nt_loads ? step_seq_kernel<true, false> : step_seq_kernel<false, false>);
-        kernel<<<env->grid, kStepBlock, lds, s>>>(A, steps, ld, ring, env->seq_screen ? 0u : ~0u);
+        kernel<<<env->grid, kStepBlock, lds, s>>>(A, steps, ld, ring | (arrive_by_code_allowed(env->dims.P, env->ports_distinct) ? kSeqDistinctPorts : 0u), env->seq_screen ? 0u : ~0u);
         HIP_TRY(hipGetLastError());
     }
     if (env->n & 3) {

@@ -112,6 +112,66 @@ __host__ __device__ __forceinline__ uint32_t gate_window_log2(uint32_t m) {
     return m <= 8 ? 3u : m <= 16 ? 2u : 1u;
 }
 
+// The window sized to the carriers: W = min(16, 64 / m) steps for 1 <= m <= 16 carrier lanes, so
+// 4 <= W <= 16 and m W <= 64 (16 steps up to 4 lanes, 12, 10, 9, 8, 7, 6, 5, 5 for 5 .. 12, 4
+// beyond). W is no power of two, so the pool's entries are offset-major: lane L = s m + c draws
+// carrier c's block for window offset s, and the split needs L / m for a wave-uniform m. That is
+// a multiply by ceil(2^16 / m) and a shift, exact for every L < 64 and m <= 16 (the quotient's
+// error is below L m / 2^16 < 1 / m), so lanes at or past m W get an offset >= W and a carrier
+// below m too: a valid block that nobody reads. gate_window_entry(m) packs both as
+// W | ceil(2^16 / m) << 8, one constant per m (one scalar load at a refill, no division);
+// m == 0 (a window without a carrier, which draws nothing): 16 | 0.
+constexpr uint32_t kGatePoolLimit = 16;   // carrier lanes up to which a wave pools (W >= 4)
+constexpr uint32_t kGatePoolSeeds = 32;   // seed rows per wave: the carriers' seeds, then their thresholds
+constexpr uint32_t kGatePoolRow = 64 + kGatePoolSeeds;  // uint4 entries per wave: the pool's 64, then the seed rows
+constexpr uint32_t kGateWindowMax = 16;
+constexpr uint32_t gate_window_entry_of(uint32_t m) {
+    return m == 0 ? kGateWindowMax : (64u / m < kGateWindowMax ? 64u / m : kGateWindowMax) | ((65535u / m + 1u) << 8);
+}
+__host__ __device__ __forceinline__ uint32_t gate_window_entry(uint32_t m) {  // m <= 16
+    constexpr auto e = gate_window_entry_of;
+    static constexpr uint32_t tab[17] = {e(0), e(1), e(2), e(3), e(4), e(5), e(6), e(7), e(8), e(9), e(10), e(11), e(12), e(13), e(14), e(15), e(16)};
+    return tab[m];
+}
+__host__ __device__ __forceinline__ uint32_t gate_window_len(uint32_t entry) { return entry & 0xffu; }
+// lane L's window offset s = L / m and carrier c = L - s m
+__host__ __device__ __forceinline__ uint32_t gate_lane_offset(uint32_t L, uint32_t entry) { return (L * (entry >> 8)) >> 16; }
+__host__ __device__ __forceinline__ uint32_t gate_lane_carrier(uint32_t L, uint32_t offset, uint32_t m) { return L - offset * m; }
+// The pool entry a lane of rank `slot` reads at offset s: its own where it is a carrier (slot < m).
+// Any lane's slot is at most m (the carriers below it), so the index is at most
+// (W - 1) m + m = m W <= 64: inside the wave's kGatePoolRow = 96 rows (the seed rows follow the pool).
+__host__ __device__ __forceinline__ uint32_t gate_pool_index(uint32_t s, uint32_t m, uint32_t slot) { return s * m + slot; }
+// That bound, checked where the library is compiled: for every m the window is 4 .. 16 steps, fills
+// at most the pool's 64 entries, and the entry of the last offset and the largest rank lies in the rows.
+constexpr bool gate_pool_reads_in_rows() {
+    for (uint32_t m = 1; m <= kGatePoolLimit; ++m) {
+        const uint32_t W = gate_window_entry_of(m) & 0xffu;
+        if (W < 4 || W > kGateWindowMax || m * W > 64 || (W - 1u) * m + m >= kGatePoolRow) return false;
+    }
+    return true;
+}
+// The refill's 64-bit ballot of screen_hot needs no fold with offset-major entries: step s is hot
+// iff bits [s m, s m + m) hold a one. The window keeps the ballot shifted right by m per step and
+// tests its low m bits (m == 0: the launch's screen_all alone, every bit of it).
+__host__ __device__ __forceinline__ uint64_t gate_screen_mask(uint32_t m) { return m != 0 ? (1ull << m) - 1ull : ~0ull; }
+__host__ __device__ __forceinline__ bool gate_screen_step(uint64_t shifted, uint64_t mask) { return (shifted & mask) != 0; }
+
+// The by-code arrival test of a launch whose ports lie on distinct cells (step_seq.h,
+// step_group_ring): port i's cell then carries code i + 1 and no other cell does, so a ship with
+// dest < P is on its destination's cell iff the code under it is dest + 1. The launch takes the
+// test only with P >= 2 (arrive_by_code_allowed): an arrival in a world of one port writes
+// pick_other's 1 = P as the new dest, which the position compare clamps to port 0 and the code never equals.
+__host__ __forceinline__ bool ports_on_distinct_cells(int P, const int32_t* px, const int32_t* py) {
+    for (int i = 0; i < P; ++i)
+        for (int k = 0; k < i; ++k)
+            if (px[i] == px[k] && py[i] == py[k]) return false;
+    return true;
+}
+__host__ __forceinline__ bool arrive_by_code_allowed(int P, bool distinct) { return distinct && P >= 2; }
+__host__ __device__ __forceinline__ bool arrive_by_code(bool do_move, uint32_t code, int dst) {
+    return do_move & (code == (uint32_t)dst + 1u);
+}
+
 // Entry c of the world image's gate thresholds: the gate of a ship with cargo c fires for a word
 // <= floor(c / max_cargo * 2^32) (random() < cargo / 50, the quotient correctly rounded and the
 // product exact), and for every word from max_cargo on. Entry 0 is 0 and the entries never fall

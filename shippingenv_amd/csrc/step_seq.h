@@ -11,6 +11,18 @@
 // Finished), step_agent.h (the packed helpers, early_draws, step_group_agent: the
 // run's last step) and step_kernel.h (step_tail_envs).
 
+// The pieces of the pooled loop that can be compiled out, each to the form before it (A/B builds:
+// SHIPENV_HIPCC_DEFINES=-DSHIPENV_SEQ_...=0; results are the same bits either way).
+#ifndef SHIPENV_SEQ_WINDOW_DIV
+#define SHIPENV_SEQ_WINDOW_DIV 1  // the window's length is min(16, 64 / m), its entries offset-major (0: 8 or 4 steps, carrier-major)
+#endif
+#ifndef SHIPENV_SEQ_CARGO_CUT
+#define SHIPENV_SEQ_CARGO_CUT 1  // a window ends only after a passed take of cargo (0: after any step whose take block ran)
+#endif
+#ifndef SHIPENV_SEQ_ARRIVE_CODE
+#define SHIPENV_SEQ_ARRIVE_CODE 1  // the regular step tests an arrival by the cell code where it may (0: by the position, always)
+#endif
+
 // The state-only step: a step of a fused sequence before its last, for a full group, Philox
 // draws, no auto-reset. Nothing can read an inner step's reward, done or err, and the next state
 // needs neither the out-of-fuel flag (a dead ship keeps moving) nor which error was raised, only
@@ -37,6 +49,7 @@ struct Carried {
     int org[4], dst[4];
     uint32_t code[4];   // the cell code under the ship, w.cell[cell_of(pos)]
     bool near;          // step_group_ring: some env of the wave is on a non-water cell (wave-uniform)
+    bool bycode;        // step_group_ring: the wave tests an arrival by the cell code (wave-uniform, set where Carried is filled)
     uint32_t thr[4];    // the gate threshold of the env's cargo, gate_thr_of(w, cargo)
     const int2* take;   // the block's stocks by cell code (stock_by_code), the same for every env
 };
@@ -255,8 +268,10 @@ __device__ __forceinline__ bool step_group_state(const LdsWorld& w, const SeqInv
 //     the lane's four carried codes, taken after the move). It is this step's arrival vote, a
 //     conservative one (it also passes for a ship that stays on a port: the test inside is the
 //     position compare, as before), and the next step's first take vote: a take passes only on a
-//     port's cell, so the exact vote over the actions runs only behind it. take_ran stays the
-//     exact vote's result (the GATE pool's windows end on it).
+//     port's cell, so the exact vote over the actions runs only behind it. The result is whether
+//     some env's cargo rose in the take block (the GATE pool's windows end on it).
+//   * behind `near` a wave with U.bycode tests an arrival by the cell code (step_lean.h,
+//     arrive_by_code); the others, and every wave of a world with two ports on one cell, by the position.
 //   * the firing gates and the arrivals stay lane masks until a wave has one: the loss and
 //     arrival blocks build their bit words themselves.
 //   * the GATE words come from `gate`. GateDrawn: the caller drew them, and the step tests them.
@@ -299,6 +314,7 @@ __device__ __forceinline__ bool step_group_ring(const LdsWorld& w, const SeqInv<
         for (int j = 0; j < 4; ++j) take_any |= (G.a[j] >= 4 + P) & (U.code[j] != 0);
         take_ran = __builtin_amdgcn_ballot_w64(take_any) != 0;
         if (take_ran) {
+            bool rose = false;  // some env of the lane took cargo
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int act = G.a[j];
@@ -307,10 +323,18 @@ __device__ __forceinline__ bool step_group_ring(const LdsWorld& w, const SeqInv<
                 const int2 st2 = U.take[U.code[j]];
                 const int stock = lt_tc ? st2.y : st2.x;
                 const bool ok_take = (act >= 4 + P) & (amount > 0) & (amount <= stock);
+                rose |= ok_take & lt_tc;
                 G.c[j] = (ok_take & lt_tc) ? G.c[j] + amount : G.c[j];
                 G.f[j] = (ok_take & !lt_tc) ? G.f[j] + (double)amount : G.f[j];
                 U.thr[j] = gate_thr_of(w, G.c[j]);
             }
+#if SHIPENV_SEQ_CARGO_CUT
+            // the result: did some env's cargo rise (a take of fuel and a refused take change no
+            // cargo, no threshold and no carrier: the pool's window and its screen stay good)
+            take_ran = __builtin_amdgcn_ballot_w64(rose) != 0;
+#else
+            (void)rose;
+#endif
         }
     }
     late(fb);
@@ -345,11 +369,27 @@ __device__ __forceinline__ bool step_group_ring(const LdsWorld& w, const SeqInv<
     U.near = near;
     uint32_t arrive = 0;
     if (near) {
-        // (a mover selects nothing, so dst is still its dest); the port's position biased as the ship's is
+        // (a mover selects nothing, so dst is still its dest)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
+        for (int j = 0; j < 4; ++j)
             if constexpr (Gate::kScreened) do_move[j] = ring_do_move((int)((uint32_t)G.a[j] - 4u), I.move_bound, here(code_t[j]));
-            arrive |= (uint32_t)(do_move[j] & (U.pos[j] == ring_bias(w.pos[min((uint32_t)dst[j], pm1)]))) << j;
+#if SHIPENV_SEQ_ARRIVE_CODE
+        // U.bycode (wave-uniform): the launch has at least two ports, all on distinct cells, and
+        // every env of the wave has dest < P, which no state-only step then undoes (a select writes
+        // val < P, an arrival pick_other's result, below P for P >= 2; with one port pick_other
+        // gives 1 = P, which the position compare clamps to port 0, so such a launch never has the
+        // bit). The ship is then on its destination's cell iff the code under it is dest + 1
+        // (step_lean.h): no position read, no clamp, no bias. Every other wave keeps the position
+        // compare: two ports may share a cell, and dest may hold anything a caller loaded.
+        if (U.bycode) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) arrive |= (uint32_t)arrive_by_code(do_move[j], U.code[j], dst[j]) << j;
+        } else
+#endif
+        {
+            // the port's position biased as the ship's is
+#pragma unroll
+            for (int j = 0; j < 4; ++j) arrive |= (uint32_t)(do_move[j] & (U.pos[j] == ring_bias(w.pos[min((uint32_t)dst[j], pm1)]))) << j;
         }
     }
     int org[4];
@@ -453,43 +493,50 @@ __device__ __forceinline__ void stock_by_code(const LdsWorld& w, int2* take) {
 // it ahead of time. When its pool is empty the wave votes: M = ballot(any of the lane's four
 // cargo > 0), m = popc(M).
 //   m == 0           no GATE draw, until a take ends the window;
-//   0 < m <= limit   a window of W steps, W the largest power of two <= 8 with m W <= 64: the
+//   0 < m <= limit   a window of W = min(16, 64 / m) steps (step_lean.h, gate_window_entry): the
 //                    carriers write their GateSeed to the wave's seed row at their rank in M,
-//                    lane L draws carrier L >> log2 W's block at counter t + (L & (W - 1)) into
-//                    pool entry L, and for W steps every lane draws FUEL alone (draw_fuel) and
-//                    reads its GATE words from entry rank W + offset (one ds_read_b128);
+//                    lane L = s m + c draws carrier c's block at counter t + s into pool entry L
+//                    (offset-major: W is no power of two), and for W steps every lane draws FUEL
+//                    alone (draw_fuel) and reads its GATE words from entry offset m + rank (one
+//                    ds_read_b128). Late in the flagship run a wave has 4 or 5 carrier lanes: a
+//                    window of 8 steps filled half the pool and the wave drew again 8 steps later;
 //   m > limit, or a wave with a lane past the last full group: kGateDirectRun steps of draw2,
 //                    then another vote.
 // A refill costs about two steps' GATE draws, so a wave whose takes keep ending its windows
 // (ships in port: right after a reset the take block runs on most wave-steps) must not refill
 // every step: after two refilled windows in a row that a take ended within kGateEarlyCut steps,
 // the wave draws directly for kGateDirectRun steps, and one more such window sends it there again.
-// cargo > 0 arises from cargo <= 0 only in a passed take of cargo, inside the take block
-// (arrival and loss only lower it), so a window ends early after a step whose take block ran
-// (step_group_state's result, a ballot: wave-uniform); the env that took did not move in that
-// step, so its gate could not fire in it. A lane that lost its cargo keeps a stale entry it no
-// longer tests. A window also ends with the run's inner steps (words drawn past them are never
-// read) and with the group. The rows are wave-private and one wave's LDS operations execute in
-// order, so there is no __syncthreads: wavefront-scope fences and wave barriers keep the
-// compiler's order. Per wave 64 pool entries and kGatePoolSeeds seed rows of 16 B.
-// The screen. The words of a window are known at its refill, up to 8 steps before they are tested,
+// Cargo rises only in a passed take of cargo, inside the take block (arrival and loss only lower
+// it), so between two such takes no env becomes a carrier and no threshold rises: a window ends
+// early after a step in which some env's cargo rose (step_group_ring's result, the ballot of
+// `ok_take & lt_tc` taken inside the take block: wave-uniform, false where the block did not run)
+// and after nothing else; the env that took did not move in that step, so its gate could not fire
+// in it. A take of fuel and a refused take change no cargo, no threshold and no carrier, and leave
+// the window standing. A lane that lost its cargo keeps a stale entry it no longer tests. A
+// window also ends with the run's inner steps (words drawn past them are never read) and with the
+// group. The rows are wave-private and one wave's LDS operations execute in order, so there is no
+// __syncthreads: wavefront-scope fences and wave barriers keep the compiler's order. Per wave 64
+// pool entries and kGatePoolSeeds seed rows of 16 B.
+// The screen. The words of a window are known at its refill, up to 16 steps before they are tested,
 // and so are the thresholds they can meet: inside a window cargo only falls, and gate_thr never
 // rises as cargo falls (step_lean.h, screen_hot). So each carrier also writes its four carried
 // thresholds to seed row kGatePoolLimit + rank (rows the limit of 16 leaves unused), the lane
-// that drew a block compares its words with that row, and the ballot, folded in scalar code to
-// one bit per window offset (screen_fold), says on which steps of the window a gate of the wave
-// can fire at all. A step whose bit is clear is cold: it reads no pool entry, tests no gate, has
-// no loss branch, and makes do_move only behind `near` (step_group_ring, GateScreened). In the
-// flagship run about 84 % of the wave-steps are cold (profiles/seq_screen/freq.json). A
-// window still ends where it did: a take by a lane that carries raises that lane's threshold,
-// and the screen would be stale. m == 0: the screen is 0. The launch's screen_all
-// (SHIPENV_SEQ_SCREEN=0: all-ones) is OR-ed into every window's screen: every step hot, the loop
-// before the screen. The direct runs test every gate.
-constexpr uint32_t kGatePoolLimit = 16;   // carrier lanes up to which a wave pools (W >= 4)
-constexpr uint32_t kGatePoolSeeds = 32;   // seed rows per wave: room for a limit of 32 (W = 2)
-constexpr uint32_t kGatePoolRow = 64 + kGatePoolSeeds;  // uint4 entries per wave
+// that drew a block compares its words with that row, and the ballot says on which steps of the
+// window a gate of the wave can fire at all: with offset-major entries step s is hot iff bits
+// [s m, s m + m) hold a one, so the window shifts the ballot down by m per step and tests its low
+// m bits (step_lean.h, gate_screen_step; no fold). A step whose bit is clear is cold: it reads no
+// pool entry, tests no gate, has no loss branch, and makes do_move only behind `near`
+// (step_group_ring, GateScreened). In the flagship run about 85 % of the wave-steps are cold
+// (profiles/seq_windows/freq.json). A window still ends where cargo rose: a take of cargo by a
+// lane that carries raises that lane's threshold, and the screen would be stale. m == 0: the
+// screen is 0. The launch's screen_all (SHIPENV_SEQ_SCREEN=0: all-ones) is OR-ed into every
+// window's screen: every step hot, the loop before the screen. The direct runs test every gate.
+// kGatePoolLimit (16 carrier lanes: W >= 4), kGatePoolSeeds (32 seed rows per wave) and kGatePoolRow
+// (64 + 32 uint4 entries per wave) are step_lean.h's, beside the window's helpers.
 constexpr uint32_t kGateDirectRun = 16;   // steps of the direct draw between two votes
 constexpr uint32_t kGateEarlyCut = 2;     // a refilled window that a take ends within this many steps was cut early
+constexpr uint32_t kSeqDistinctPorts = 1; // step_seq_kernel's ring_bytes, bit 0: at least two ports, all on distinct cells
+static_assert(gate_pool_reads_in_rows(), "GATE pool: a window's reads lie in the wave's rows");  // the host's check (step_lean.h)
 constexpr size_t kGatePoolBytes = (kStepBlock / 64) * kGatePoolRow * sizeof(uint4);  // 6 KiB
 constexpr int kRingRows = 3;  // (ring_r0 .. ring_r2) 16-byte units of the bordered cell table a thread loads ahead: 12 KiB, the 100 x 100 map's 10.2
 static_assert(kGatePoolLimit <= kGatePoolSeeds && kGatePoolLimit <= 32, "GATE pool: a window of at least 2 steps");
@@ -532,8 +579,11 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
     if (steps <= 0) return;  // nothing to store (the host launches no empty run)
     // The bordered cell table (step_lean.h) follows the image in the world buffer; ring_bytes == 0:
     // this launch has none (launch-uniform), and every wave runs the general step.
+    // Bit 0 of ring_bytes (kSeqDistinctPorts; the table's size is a multiple of 16): the host found
+    // at least two ports, all on distinct cells, so a regular wave may test arrivals by the cell code.
     const uint32_t ring16 = steps > 1 ? ring_bytes >> 4 : 0u;
     const bool has_ring = ring16 != 0;
+    [[maybe_unused]] const bool distinct = (ring_bytes & kSeqDistinctPorts) != 0;
     const int64_t full = A.n >> 2;
     const int64_t first = (int64_t)blockIdx.x * A.iters * kStepBlock;  // block-uniform first group
 
@@ -616,6 +666,16 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
             }
             const bool ring = has_ring && __builtin_amdgcn_ballot_w64(irregular) == 0;  // wave-uniform
             U.near = __builtin_amdgcn_ballot_w64((U.code[0] | U.code[1] | U.code[2] | U.code[3]) != 0) != 0;
+            // the arrival test by the cell code (step_group_ring): the launch's bit and one ballot
+            U.bycode = false;
+#if SHIPENV_SEQ_ARRIVE_CODE
+            if (distinct) {  // launch-uniform
+                bool past = false;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) past |= (uint32_t)U.dst[j] >= (uint32_t)w.P;
+                U.bycode = __builtin_amdgcn_ballot_w64(past) == 0;
+            }
+#endif
             if (ring) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) U.pos[j] = ring_bias(U.pos[j]);
@@ -682,9 +742,73 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                             pooled = false;
                             break;
                         }
+                        const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
+#if SHIPENV_SEQ_WINDOW_DIV
+                        // the window: W = min(16, 64 / m) steps, and the multiplier of a lane's L / m (step_lean.h)
+                        const uint32_t went = gate_window_entry(m);
+                        // the window's screen: the refill's ballot itself, m bits per offset (step_lean.h), shifted
+                        // down by m per step: can a gate fire on this step? m == 0: no, however long the
+                        // window. screen_all (SHIPENV_SEQ_SCREEN=0): every step is hot.
+                        uint64_t screen = (uint64_t)(int64_t)(int32_t)screen_all;
+                        const uint64_t smask = gate_screen_mask(m);
+                        if (m != 0) {
+                            if (carry) {
+                                seeds[slot] = make_uint4(inv.c3, inv.hi[1], inv.lo[1], qk.e1);
+                                // the thresholds at the vote (0 for an env without cargo: gate_thr's entry 0)
+                                seeds[kGatePoolLimit + slot] = make_uint4(U.thr[0], U.thr[1], U.thr[2], U.thr[3]);
+                            }
+                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                            __builtin_amdgcn_wave_barrier();
+                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                            // lane L = so m + of draws carrier of's block at window offset so; the lanes at
+                            // or past m W: a carrier's block at an offset past the window, which nobody reads
+                            const uint32_t so = gate_lane_offset(L, went), of = gate_lane_carrier(L, so, m);
+                            const uint4 sd = seeds[of];
+                            const uint4 th = seeds[kGatePoolLimit + of];
+                            const U4 gw = draw_gate_pooled_sched(I.ks, GateSeed{sd.x, sd.y, sd.z, sd.w}, t + so);
+                            pool[L] = make_uint4(gw.v[0], gw.v[1], gw.v[2], gw.v[3]);
+                            // screen_hot (step_lean.h) word by word: four compares into lane masks, OR-ed in scalar code
+                            screen |= __builtin_amdgcn_ballot_w64(gw.v[0] <= th.x) | __builtin_amdgcn_ballot_w64(gw.v[1] <= th.y) |
+                                      __builtin_amdgcn_ballot_w64(gw.v[2] <= th.z) | __builtin_amdgcn_ballot_w64(gw.v[3] <= th.w);
+                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                            __builtin_amdgcn_wave_barrier();
+                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        }
+                        // a carrier's words for offset s are entry s m + slot < m W <= 64. Another lane's
+                        // slot is at most m: it reads an entry up to m W <= 64 < kGatePoolRow (the seeds
+                        // follow the pool; a static_assert checks the bound for every m), whose words its gate
+                        // never tests. m == 0: entry 0; no entry holds anything, no gate tests a word, and
+                        // the window lasts until a take of cargo ends it.
+                        const uint32_t win = m != 0 ? min(tl - t, gate_window_len(went)) : tl - t;  // t may wrap 2^32 inside the run
+                        uint32_t s = 0;
+                        bool took;
+                        do {
+                            row += ld;
+                            int32_t nxt[4];
+                            ld4_full<kNt>(row, g0, nxt, lane);
+                            // the lane's words, read on a hot step only (the offset read as the hot branch
+                            // sees it: the entry's address is made there, not stepped by m on every step)
+                            const auto words = [&]() {
+                                uint32_t so = s;
+                                asm volatile("" : "+s"(so));
+                                const uint4 g4 = pool[gate_pool_index(so, m, slot)];
+                                return U4{{g4.x, g4.y, g4.z, g4.w}};
+                            };
+                            // FUEL alone, drawn after the take block (the step's `late`)
+                            const auto fuel = [&](U4& fb) {
+                                fb = draw_fuel_sched(I.ks, qk, inv, t);
+                                asm volatile("" : "+v"(fb.v[0]), "+v"(fb.v[1]), "+v"(fb.v[2]), "+v"(fb.v[3]));
+                            };
+                            took = step_group_ring(w, I, qk, t, U4{}, GateScreened<decltype(words)>{gate_screen_step(screen, smask), words}, G, U, fuel);
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
+                            screen >>= m;
+                            ++s;
+                            ++t;
+                        } while (!took && s != win);
+#else
                         // the window: the largest power of two W <= 8 with m W <= 64
                         const uint32_t logw = gate_window_log2(m);
-                        const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
                         const uint32_t wmask = (1u << logw) - 1u;
                         // the window's screen, one bit per offset (step_lean.h): can a gate fire there?
                         // m == 0: no, however long the window (0 or all-ones: any bit of it will do).
@@ -745,6 +869,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                             ++s;
                             ++t;
                         } while (!took && s != win);
+#endif
                         // refilled windows in a row that a take cut early
                         cuts = took && m != 0 && s <= kGateEarlyCut ? cuts + 1u : 0u;
                     } while (t != tl);

@@ -1,18 +1,22 @@
 """How often the screened GATE pool's steps are hot, on the C oracle alone (no GPU):
 
-    python tools/screen_freq.py [--envs 32768] [--steps 1000] > profiles/seq_screen/freq.json
+    python tools/screen_freq.py [--envs 32768] [--steps 1000] > profiles/seq_windows/freq.json
+    python tools/screen_freq.py --rule parent      (the windows before: profiles/seq_screen/freq.json)
 
 The bench's config 3 (Philox draws, the 5 default ports, seed 2026, its own action rows: the
 pre-roll's at t = 1000000 + k, the warm-up's and the timed ones from row 0), stepped from reset
 through the 1000-step pre-roll and the 50 warm-up steps, then `--steps` timed steps as one fused
 launch. A wave is 256 consecutive envs (64 lanes of 4). The kernel's windows are modelled as
-step_seq.h runs them (the vote, W = 8 up to 8 carrier lanes and 4 up to 16, the direct run above
-16 or after two early cuts, a take ends a window), and for every pooled window the GATE words
+step_seq.h runs them (the vote, W = min(16, 64 / m) steps for m <= 16 carrier lanes, the direct run
+above 16 or after two early cuts, a passed take of cargo ends a window; --rule parent: W = 8 up to 8
+carrier lanes and 4 up to 16, and any step whose take block ran ends a window), and for every pooled window the GATE words
 themselves are drawn (Philox4x32-10 in numpy, checked against the oracle's) and screened against
 the carriers' thresholds at the vote, as the refill does. Per wave-step: is its screen bit set,
-does a gate fire (the exact test), does a fire follow a fall of cargo inside the window; and the
-rarer events of the step (the take block, a passed take of cargo, `near`, an arrival, a loss).
-It asserts that no fire falls on a cold step.
+does a gate fire (the exact test), does a fire follow a fall of cargo inside the window; the hot
+steps past window offset 7 and the take blocks that leave their window standing (a take of fuel, a
+refused take); and the rarer events of the step (the take block, a passed take of cargo, `near`,
+an arrival, a loss). It asserts that cargo never rises inside a window and that no fire falls on
+a cold step.
 """
 import argparse
 import json
@@ -50,6 +54,7 @@ def main():
     ap.add_argument("--seed", type=int, default=2026)
     ap.add_argument("--preroll", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--rule", choices=("windows", "parent"), default="windows")
     args = ap.parse_args()
 
     from oracle import oracle as O
@@ -92,7 +97,7 @@ def main():
     vote = np.zeros(n, np.int64)  # cargo at the wave's vote
     marks = [m for m in (100, 500, args.steps) if m <= args.steps]
     names = ("pooled", "no_carrier", "direct", "hot", "hot_fire", "hot_no_fire", "cold", "fire_after_fall_wave_steps", "refills",
-             "loss_lowers_cargo", "take_block", "take_cargo_passed", "near", "arrival")
+             "loss_lowers_cargo", "take_block", "take_cargo_passed", "near", "arrival", "hot_past_offset_7", "take_block_inside_window")
     c = dict.fromkeys(names, 0)
     rows = []
     inner = args.steps - 1  # the launch's last step is the full one
@@ -109,7 +114,7 @@ def main():
             cuts[direct] = np.minimum(cuts[direct], 1)
             pool = v & ~direct
             mode[pool] = np.where(m[pool] != 0, 1, 0)
-            W[pool] = np.where(m[pool] <= 8, 8, 4)
+            W[pool] = np.where(m[pool] <= 8, 8, 4) if args.rule == "parent" else np.minimum(16, 64 // np.maximum(m[pool], 1))
             s[pool] = 0
             c["refills"] += int((pool & (m != 0)).sum())
             ve = np.repeat(v, WAVE)
@@ -123,7 +128,9 @@ def main():
         arrived = mover & (st.origin != org0)
         c["loss_lowers_cargo"] += int(per_wave((st.cargo < cargo0) & ~arrived).sum())
         c["take_block"] += int(took.sum())
-        c["take_cargo_passed"] += int(per_wave(ok & (a >= 4 + P) & (a < 54 + P) & (st.cargo > cargo0)).sum())
+        rose = per_wave(ok & (a >= 4 + P) & (a < 54 + P) & (st.cargo > cargo0))
+        c["take_cargo_passed"] += int(rose.sum())
+        cut = took if args.rule == "parent" else rose  # what ends a window
         c["near"] += int(per_wave(code[st.x, st.y] != 0).sum())
         c["arrival"] += int(per_wave(arrived).sum())
         if k < inner:
@@ -151,11 +158,13 @@ def main():
             c["hot_no_fire"] += int((pooled & hot & ~fire).sum())
             c["cold"] += int((pooled & ~hot).sum() + (mode == 0).sum())
             c["fire_after_fall_wave_steps"] += int(per_wave(fire_e & (cargo0 < vote)).sum())
+            c["hot_past_offset_7"] += int((pooled & hot & (s >= 8)).sum())
+            c["take_block_inside_window"] += int(((mode != 2) & took & ~cut).sum())
             # the end of a window
             s += 1
             left -= mode == 2
-            end_pool = (mode != 2) & (took | ((mode == 1) & (s == W)))
-            early = (mode == 1) & took & (s <= EARLY_CUT)
+            end_pool = (mode != 2) & (cut | ((mode == 1) & (s == W)))
+            early = (mode == 1) & cut & (s <= EARLY_CUT)
             cuts = np.where(end_pool, np.where(early, cuts + 1, 0), cuts)
             need_vote = end_pool | ((mode == 2) & (left == 0))
         t += 1
@@ -165,7 +174,7 @@ def main():
             row = {"timed_steps": k + 1, "wave_steps": ws}
             row.update({f"share_{x}": round(c[x] / ws, 4) for x in ("loss_lowers_cargo", "take_block", "take_cargo_passed", "near", "arrival")})
             row.update({f"share_{x}": round(c[x] / wi, 4) for x in ("pooled", "no_carrier", "direct", "hot", "hot_fire", "hot_no_fire", "cold",
-                                                                    "fire_after_fall_wave_steps")})
+                                                                    "fire_after_fall_wave_steps", "hot_past_offset_7", "take_block_inside_window")})
             row["steps_per_refill"] = round(c["pooled"] / max(c["refills"], 1), 2)
             rows.append(row)
             print(row, file=sys.stderr, flush=True)
@@ -174,7 +183,7 @@ def main():
                        "below its env's threshold at the vote; cold: the others, which test no gate); C oracle, Philox draws, 5 default "
                        "ports, the bench's action rows, after its pre-roll and warm-up. hot and cold are shares of all inner wave-steps; "
                        "a direct wave-step runs the full gate test.",
-               "envs": n, "seed": args.seed, "preroll": args.preroll, "warmup": args.warmup, "by_timed_steps": rows}, sys.stdout, indent=1)
+               "rule": args.rule, "envs": n, "seed": args.seed, "preroll": args.preroll, "warmup": args.warmup, "by_timed_steps": rows}, sys.stdout, indent=1)
     print()
 
 
