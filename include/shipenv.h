@@ -189,7 +189,9 @@ int se_step(se_env* env, const int32_t* actions, void* stream);
  * draws it for every lane every step instead. The results are the same bits.
  * A wave all of whose envs are inside the map and have a destination steps on a copy of the cell
  * codes with a border of one cell around the map (LDS behind the pools; 10.2 KiB for a 100 x 100
- * map): a move off the map reads the border's code, so such a step has no bounds test. Worlds
+ * map): a move off the map reads the border's code, so such a step has no bounds test. On maps
+ * up to 125 cells wide such a wave carries each ship's position as its cell's address in that
+ * copy, and a move adds a byte from four per-direction deltas kept behind it (16 bytes). Worlds
  * of more than 253 ports, worlds whose table would leave fewer than four workgroups on a compute
  * unit, and every world under SHIPENV_SEQ_RING=0 at se_create have no such table; their waves,
  * and any wave with an env loaded outside the map or without a destination, run the general

@@ -432,12 +432,21 @@ int launch_step_seq(se_env* env, const int32_t* act, int64_t ld, int32_t steps, 
         const bool pool = env->seq_gate_pool && base + kGatePoolBytes <= kLdsDefault;
         // then the bordered cell table, where the world has one and four workgroups still share a CU
         const size_t without = base + (pool ? kGatePoolBytes : 0);
-        const uint32_t ring = env->seq_ring && ring_table_fits(env->dims.H, env->dims.W, env->dims.P, without)
+        // (with the move deltas behind it: kRingDeltaBytes, whichever form the launch's regular waves take)
+        const uint32_t ring = env->seq_ring && ring_table_fits(env->dims.H, env->dims.W, env->dims.P, without + kSeqDeltaBytes)
                                   ? ring_table_bytes(env->dims.H, env->dims.W) : 0u;
-        const size_t lds = without + ring;
-        const auto kernel = pool ? (env->nt_loads ? step_seq_kernel<true, true> : step_seq_kernel<false, true>)
-                                 : (env->nt_loads ? step_seq_kernel<true, false> : step_seq_kernel<false, false>);
-        kernel<<<env->grid, kStepBlock, lds, s>>>(A, steps, ld, ring | (arrive_by_code_allowed(env->dims.P, env->ports_distinct) ? kSeqDistinctPorts : 0u), env->seq_screen ? 0u : ~0u);
+        const size_t lds = without + ring + (ring ? kSeqDeltaBytes : 0);
+        // the carried cell address: a launch with the table whose move deltas are bytes
+        const bool addr = SHIPENV_SEQ_CELL_ADDR && ring != 0 && ring_byte_deltas(env->dims.W);
+        auto kernel = pool ? (env->nt_loads ? step_seq_kernel<true, true, false> : step_seq_kernel<false, true, false>)
+                           : (env->nt_loads ? step_seq_kernel<true, false, false> : step_seq_kernel<false, false, false>);
+#if SHIPENV_SEQ_CELL_ADDR
+        if (addr)
+            kernel = pool ? (env->nt_loads ? step_seq_kernel<true, true, true> : step_seq_kernel<false, true, true>)
+                          : (env->nt_loads ? step_seq_kernel<true, false, true> : step_seq_kernel<false, false, true>);
+#endif
+        kernel<<<env->grid, kStepBlock, lds, s>>>(A, steps, ld, ring | (arrive_by_code_allowed(env->dims.P, env->ports_distinct) ? kSeqDistinctPorts : 0u), env->seq_screen ? 0u : ~0u,
+                                                  addr ? ring_unindex_mul(env->dims.W) : 0u);
         HIP_TRY(hipGetLastError());
     }
     if (env->n & 3) {

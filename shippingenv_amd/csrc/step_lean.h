@@ -3,7 +3,8 @@
 // host with the forms they replaced (the error cascade's terms, the select of -scale / -0.0),
 // tools/step_trim_check.cpp the move test on val, the fuel scale's FMA and the GATE pool's
 // window choice, tools/step_ring_check.cpp the regular step's decode on the bordered cell
-// table with the general form's, and tools/step_screen_check.cpp the GATE pool's screen.
+// table with the general form's, tools/step_screen_check.cpp the GATE pool's screen, and
+// tools/step_addr_check.cpp the carried cell address with the packed position.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -86,6 +87,31 @@ __host__ __device__ __forceinline__ bool ring_do_move(int val, uint32_t bound, u
 }
 __host__ __device__ __forceinline__ bool ring_moved(int val, uint32_t bound, uint32_t code) {
     return ((uint32_t)val > bound) & (code < kRingBorder);
+}
+
+// The carried cell address (step_seq.h, step_group_ring<kAddr>). A regular wave's inner steps read
+// a ship's x and y only to make the target's index in the table again, so the position is carried
+// as that index plus the table's LDS address, and a move adds one signed delta, dx (W + 2) + dy, read
+// from a four-entry table that the launch derives from the image's packed moves. Up to W = 125 the
+// deltas are bytes (|dx (W + 2) + dy| <= 127) and the entry's address is (act & 3) | base in one
+// instruction, so the table sits at a 4-byte-aligned address, behind the bordered table
+// (kRingDeltaBytes of the launch's LDS, counted where the host asks ring_table_fits). Wider maps
+// keep the packed position (another instantiation of the kernel, chosen by the host).
+// After the inner steps the index goes back to x + 1 | y + 1 << 16 once: a division by W + 2 as a
+// multiply by ceil(2^32 / (W + 2)) and the product's high word, exact while index (W + 2) < 2^32
+// (the quotient's error is below index (W + 2) / 2^32 / (W + 2)); tools/step_addr_check.cpp
+// compares it with / and % for every W and every index a table of that width can hold.
+constexpr size_t kRingDeltaBytes = 16;
+__host__ __device__ __forceinline__ bool ring_byte_deltas(int W) { return W + 2 <= 127; }
+// the delta of a packed move dx | dy << 16 (16-bit halves, -1 as 0xffff)
+__host__ __device__ __forceinline__ int ring_delta(uint32_t mv, int W) {
+    return (int)(int16_t)(mv & 0xffffu) * (W + 2) + (int)(int16_t)(mv >> 16);
+}
+__host__ __device__ __forceinline__ uint32_t ring_unindex_mul(int W) { return 0xffffffffu / (uint32_t)(W + 2) + 1u; }
+// index -> the biased position (x + 1) | (y + 1) << 16; mul: ring_unindex_mul(W)
+__host__ __device__ __forceinline__ uint32_t ring_unindex(uint32_t index, int W, uint32_t mul) {
+    const uint32_t q = (uint32_t)(((uint64_t)index * mul) >> 32);
+    return q | ((index - q * (uint32_t)(W + 2)) << 16);
 }
 
 // fuel - (moved ? scale : 0) with the bits of fuel + (moved ? -scale : -0.0): (-scale) * 1 is

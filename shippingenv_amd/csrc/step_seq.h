@@ -22,6 +22,9 @@
 #ifndef SHIPENV_SEQ_ARRIVE_CODE
 #define SHIPENV_SEQ_ARRIVE_CODE 1  // the regular step tests an arrival by the cell code where it may (0: by the position, always)
 #endif
+#ifndef SHIPENV_SEQ_CELL_ADDR
+#define SHIPENV_SEQ_CELL_ADDR 1  // a regular wave of a map up to 125 wide carries the ship's cell address in the bordered table (0: the packed position, always)
+#endif
 
 // The state-only step: a step of a fused sequence before its last, for a full group, Philox
 // draws, no auto-reset. Nothing can read an inner step's reward, done or err, and the next state
@@ -45,7 +48,8 @@
 // (profiles/seq_guard/freq.json). The result says whether the take block ran (wave-uniform): the
 // only place where an env's cargo can become positive, which the caller's GATE pool needs.
 struct Carried {
-    uint32_t pos[4];  // x | y << 16; in a regular wave (step_group_ring) biased: x + 1 | y + 1 << 16
+    uint32_t pos[4];  // x | y << 16; in a regular wave (step_group_ring) biased: x + 1 | y + 1 << 16, or (kAddr) the LDS
+                      // address of the ship's cell in the bordered table: ring0 + (x + 1) (W + 2) + (y + 1)
     int org[4], dst[4];
     uint32_t code[4];   // the cell code under the ship, w.cell[cell_of(pos)]
     bool near;          // step_group_ring: some env of the wave is on a non-water cell (wave-uniform)
@@ -70,6 +74,7 @@ struct SeqInv {
     KeySched ks;
     uint32_t move_bound;
     uint32_t ring0;  // the bordered cell table's LDS address (step_group_ring)
+    uint32_t delta0; // the move deltas' LDS address, 4-byte aligned (step_group_ring<kAddr>)
     __device__ __forceinline__ U4 block(const Key& qk, uint32_t t, uint32_t slot) const {
         if constexpr (kSched) return draw_sched(ks, qk, t, slot);
         else return draw(qk, t, slot);
@@ -301,7 +306,15 @@ struct GateScreened {
     __device__ __forceinline__ bool hot() const { return is_hot; }
     __device__ __forceinline__ U4 words() const { return read(); }
 };
-template <bool kNt, bool kSched, typename Gate, typename Late = NoLateDraw>
+// kAddr: U.pos is the cell's LDS address (step_lean.h): the target is the address plus the action's
+// delta, and its code the byte there.
+typedef __attribute__((address_space(3))) const int8_t lds_i8;
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) const u32x2 lds_u32x2;
+__device__ __forceinline__ uint32_t ring_address(uint32_t ring0, uint32_t bp, uint32_t wh) {
+    return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, bp), __builtin_bit_cast(u16x2, wh), ring0, false);
+}
+template <bool kAddr, bool kNt, bool kSched, typename Gate, typename Late = NoLateDraw>
 __device__ __forceinline__ bool step_group_ring(const LdsWorld& w, const SeqInv<kSched>& I, const Key& qk, uint32_t t, U4 fb,
                                                 const Gate& gate, Group<false, false, kNt>& G, Carried& U, Late late = Late{}) {
     const int P = w.P;
@@ -342,8 +355,14 @@ __device__ __forceinline__ bool step_group_ring(const LdsWorld& w, const SeqInv<
     // MOVE: the four lookups at the targets first, in flight together
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        np[j] = pk_add_u16(U.pos[j], w.moves[G.a[j] & 3]);
-        code_t[j] = lds_cell(I.ring0, np[j], wh);
+        if constexpr (kAddr) {
+            const int8_t d = *(lds_i8*)(uintptr_t)(((uint32_t)G.a[j] & 3u) | I.delta0);
+            np[j] = U.pos[j] + (uint32_t)(int32_t)d;
+            code_t[j] = *(lds_u8*)(uintptr_t)np[j];
+        } else {
+            np[j] = pk_add_u16(U.pos[j], w.moves[G.a[j] & 3]);
+            code_t[j] = lds_cell(I.ring0, np[j], wh);
+        }
     }
     asm("" : "+v"(code_t[0]), "+v"(code_t[1]), "+v"(code_t[2]), "+v"(code_t[3]));
     int dst[4], cg[4];
@@ -387,9 +406,18 @@ __device__ __forceinline__ bool step_group_ring(const LdsWorld& w, const SeqInv<
         } else
 #endif
         {
-            // the port's position biased as the ship's is
+            // the port's position biased as the ship's is (kAddr: its cell's address, made here from the
+            // table's address and (W + 2) | 1 << 16 as the words behind the deltas hold them: nothing
+            // else in a step reads either, and kept in scalar registers for this branch alone they
+            // were spilled and read back inside the loop)
+            [[maybe_unused]] u32x2 rw = {0u, 0u};
+            if constexpr (kAddr) rw = *(lds_u32x2*)(uintptr_t)(I.delta0 + 8u);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) arrive |= (uint32_t)(do_move[j] & (U.pos[j] == ring_bias(w.pos[min((uint32_t)dst[j], pm1)]))) << j;
+            for (int j = 0; j < 4; ++j) {
+                uint32_t port = ring_bias(w.pos[min((uint32_t)dst[j], pm1)]);
+                if constexpr (kAddr) port = ring_address(rw.x, port, rw.y);
+                arrive |= (uint32_t)(do_move[j] & (U.pos[j] == port)) << j;
+            }
         }
     }
     int org[4];
@@ -539,6 +567,7 @@ constexpr uint32_t kSeqDistinctPorts = 1; // step_seq_kernel's ring_bytes, bit 0
 static_assert(gate_pool_reads_in_rows(), "GATE pool: a window's reads lie in the wave's rows");  // the host's check (step_lean.h)
 constexpr size_t kGatePoolBytes = (kStepBlock / 64) * kGatePoolRow * sizeof(uint4);  // 6 KiB
 constexpr int kRingRows = 3;  // (ring_r0 .. ring_r2) 16-byte units of the bordered cell table a thread loads ahead: 12 KiB, the 100 x 100 map's 10.2
+constexpr size_t kSeqDeltaBytes = SHIPENV_SEQ_CELL_ADDR ? kRingDeltaBytes : 0;  // the move deltas behind the table (step_lean.h)
 static_assert(kGatePoolLimit <= kGatePoolSeeds && kGatePoolLimit <= 32, "GATE pool: a window of at least 2 steps");
 static_assert(2 * kGatePoolLimit <= kGatePoolSeeds, "GATE pool: the carriers' threshold rows follow their seed rows");
 
@@ -572,9 +601,13 @@ __device__ __forceinline__ uint32_t seq_lane() {
     return lane;
 }
 
-template <bool kNt, bool kPool>
+// kAddr (the host's choice, for a launch with the table and byte deltas: step_lean.h): the regular
+// waves carry the cell address. Four threads derive the move deltas from the image's packed moves
+// into the kRingDeltaBytes behind the table, and ring_inv is ring_unindex_mul(W), for the way back
+// to x, y after the inner steps.
+template <bool kNt, bool kPool, bool kAddr>
 __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4))) void step_seq_kernel(
-    StepArgs A, int32_t steps, int64_t ld, uint32_t ring_bytes, uint32_t screen_all) {
+    StepArgs A, int32_t steps, int64_t ld, uint32_t ring_bytes, uint32_t screen_all, uint32_t ring_inv) {
     extern __shared__ uint32_t lds[];
     if (steps <= 0) return;  // nothing to store (the host launches no empty run)
     // The bordered cell table (step_lean.h) follows the image in the world buffer; ring_bytes == 0:
@@ -618,6 +651,14 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
             if (threadIdx.x + kStepBlock < ring16) ring_l[threadIdx.x + kStepBlock] = ring_r1;
             if (threadIdx.x + 2 * kStepBlock < ring16) ring_l[threadIdx.x + 2 * kStepBlock] = ring_r2;
             for (uint32_t i = threadIdx.x + kStepBlock * kRingRows; i < ring16; i += kStepBlock) ring_l[i] = ring_g[i];  // larger maps
+            if constexpr (kAddr) {
+                // the move deltas, one byte per direction, behind the table's last 16-byte unit; in its
+                // second half the table's own LDS address and the index's dot-product factor, for the
+                // arrival test by address
+                if (threadIdx.x < 4) reinterpret_cast<int8_t*>(ring_l + ring16)[threadIdx.x] = (int8_t)ring_delta(w.moves[threadIdx.x], w.W);
+                if (threadIdx.x == 4)
+                    reinterpret_cast<uint2*>(ring_l + ring16)[1] = make_uint2(lds_address(reinterpret_cast<const uint8_t*>(ring_l)), (uint32_t)(w.W + 2) | (1u << 16));
+            }
         }
         __syncthreads();
     }
@@ -628,6 +669,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
         I.move_bound = lean_move_bound(w.P);
         asm volatile("" : "+s"(I.move_bound));
         I.ring0 = lds_address(reinterpret_cast<const uint8_t*>(ring_l));
+        I.delta0 = lds_address(reinterpret_cast<const uint8_t*>(ring_l + ring16));
     }
 
     BlockStats bs;
@@ -678,7 +720,10 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
 #endif
             if (ring) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) U.pos[j] = ring_bias(U.pos[j]);
+                for (int j = 0; j < 4; ++j) {
+                    U.pos[j] = ring_bias(U.pos[j]);
+                    if constexpr (kAddr) U.pos[j] = ring_address(I.ring0, U.pos[j], (uint32_t)(w.W + 2) | (1u << 16));
+                }
             }
             // the step-invariant parts of the quad's FUEL and GATE blocks (philox.h, draw2),
             // opaque so the loop keeps them in registers as computed here
@@ -708,7 +753,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                     int32_t nxt[4];
                     ld4_full<kNt>(row, g0, nxt);
                     const U4x2 fg = draw2(qk, inv, t);
-                    step_group_ring(w, I, qk, t, fg.fuel, GateDrawn{fg.gate}, G, U);
+                    step_group_ring<kAddr>(w, I, qk, t, fg.fuel, GateDrawn{fg.gate}, G, U);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
                 }
@@ -799,7 +844,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                                 fb = draw_fuel_sched(I.ks, qk, inv, t);
                                 asm volatile("" : "+v"(fb.v[0]), "+v"(fb.v[1]), "+v"(fb.v[2]), "+v"(fb.v[3]));
                             };
-                            took = step_group_ring(w, I, qk, t, U4{}, GateScreened<decltype(words)>{gate_screen_step(screen, smask), words}, G, U, fuel);
+                            took = step_group_ring<kAddr>(w, I, qk, t, U4{}, GateScreened<decltype(words)>{gate_screen_step(screen, smask), words}, G, U, fuel);
 #pragma unroll
                             for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
                             screen >>= m;
@@ -863,7 +908,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                                 fb = draw_fuel_sched(I.ks, qk, inv, t);
                                 asm volatile("" : "+v"(fb.v[0]), "+v"(fb.v[1]), "+v"(fb.v[2]), "+v"(fb.v[3]));
                             };
-                            took = step_group_ring(w, I, qk, t, U4{}, GateScreened<decltype(words)>{((screen >> (s & 31u)) & 1u) != 0, words}, G, U, fuel);
+                            took = step_group_ring<kAddr>(w, I, qk, t, U4{}, GateScreened<decltype(words)>{((screen >> (s & 31u)) & 1u) != 0, words}, G, U, fuel);
 #pragma unroll
                             for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
                             ++s;
@@ -880,7 +925,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
                         int32_t nxt[4];
                         ld4_full<kNt>(row, g0, nxt, lane);
                         const U4x2 fg = draw2(qk, inv, t);
-                        step_group_ring(w, I, qk, t, fg.fuel, GateDrawn{fg.gate}, G, U);
+                        step_group_ring<kAddr>(w, I, qk, t, fg.fuel, GateDrawn{fg.gate}, G, U);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) G.a[j] = nxt[j];
                     }
@@ -888,7 +933,10 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(4)))
             }
             if (ring) {  // the bias comes off once
 #pragma unroll
-                for (int j = 0; j < 4; ++j) U.pos[j] = ring_unbias(U.pos[j]);
+                for (int j = 0; j < 4; ++j) {
+                    if constexpr (kAddr) U.pos[j] = ring_unindex(U.pos[j] - I.ring0, w.W, ring_inv);
+                    U.pos[j] = ring_unbias(U.pos[j]);
+                }
             }
             // back into the Group's packed bytes
             pack_pos(U.pos, G.x, G.y);
