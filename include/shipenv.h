@@ -782,6 +782,76 @@ int se_policy_f32(se_qnet* q, int32_t* actions, double epsilon, uint32_t t, floa
 int se_qnet_repack(se_qnet* q, int32_t* bump, void* stream);
 int se_qnet_destroy(se_qnet* q);  /* destroy a qnet before the env it was created on */
 
+/* Network-policy rollouts (an extension: the reference values its DQN only by stepping the
+ * training envs; what it has is restated exactly: choose_action, and the training loop's break on
+ * a raising step): what env src[r] earns if it plays the packed network from where it stands,
+ * without playing it. Rollout r copies env src[r] (the env's state and counters are only read)
+ * and plays positions k = 0 .. steps - 1 on the private ship s under the key (seed, ids ? ids[r] :
+ * rollout_base + r). The position:
+ *   1. d = the block (k, slot 12), the block every rollout kind draws at position k. Word 0, the
+ *      random policy's sample word, is not read; words 1-3 are u_fuel, u_gate, u_type.
+ *   2. The action is choose_action (agents/dqn.py:177-203) on s, exactly as se_policy does it for
+ *      an env in that state: the observation row's 6 live inputs (x, y, fuel as f64 -> f32 -> bf16
+ *      hi + lo, "cargo" = fuel, origin, dest; the port block folded into fc1's bias), and the
+ *      first maximum of Q over is_valid_action. If epsilon > 0, one block is drawn at (k, slot 22)
+ *      and the position explores iff word0 * 2^-32 <= epsilon (se_policy's non-strict test, not the
+ *      table rollout's strict one), word 1 then picking the j-th valid action, ascending, with
+ *      uniform_int(word1, 4 + nsel + cst + fst); with epsilon == 0 slot 22 is not drawn at all.
+ *      Word 0 of slot 22 is the table rollout's explore uniform, so equal ids explore at the same
+ *      positions in both (up to the one word value that separates < from <=).
+ *   3. The agent index is stepped as se_rollout_plan steps position k of an agent-index plan: d's
+ *      words 1-3 and, for a partial loss or an arrival, the block (k, slot 13).
+ *   4. A counted step adds its f64 reward to ret[r] in order and 1 to counted[r]; one that reports
+ *      done ends the rollout with SE_PLAN_DONE.
+ *   5. A raising step ends the rollout, as the reference's loop breaks on one (agents/dqn.py:
+ *      309-313; its `continue` case, "Destination port must be different", is masked out by
+ *      is_valid_action, so no chosen action reaches it): the ship is left untouched, the raise
+ *      counts 1 in end.raised with first_err and first_err_at = k, and the status is
+ *      SE_PLAN_RAISED. This is what se_replay_end's cut does to a training episode. Under the mask
+ *      the reachable raises are a move with no destination and a move off the map.
+ *   6. Running out of positions is SE_PLAN_END. steps = 0 writes ret 0, counted 0 and
+ *      SE_PLAN_END; a bad src[r] writes SE_PLAN_BAD_SRC with the zeros and -1 se_rollout_plan
+ *      writes.
+ * What follows. The plan equality: for any epsilon the rollout equals se_rollout_plan under the
+ * same ids, in its agent-index encoding, fed the actions it emitted with len[r] = counted + raised,
+ * in ret (bits), counted, raised, first_err, first_err_at, the end ship and DONE / END (a RAISED
+ * rollout reads as END there). The policy equality: the action of position k is se_policy's action
+ * for an env holding the rollout's ship before position k (an explored position: se_policy with
+ * epsilon 1 picks by its own word what this picks by slot 22's word 1, the same choice law).
+ *
+ * mode 0 plays the bf16 network as se_policy evaluates it, from the packed image of the last
+ * se_qnet_set_weights / se_qnet_repack. mode 1, the fp32-faithful network of se_policy_f32, is not
+ * built: SE_EINVAL ("the fp32-faithful rollout is not built").
+ *
+ * Buffers (device): src, m entries, and ids, m entries or NULL, are only read; ret, counted and
+ * status, m entries each, are written whole; of `out` (NULL: nothing more is wanted) every
+ * pointer that is not NULL gets m entries (explored and the nine of `end`), and act gets elements
+ * 0 .. m - 1 of each of its `steps` rows of stride ld (step-major, element k * ld + r, as
+ * se_rollout_plan reads agent indices: the action of position k, and SE_QROLL_PAD for a position
+ * not played and a bad source); the ld - m columns behind a row are neither read nor written. The
+ * call reads the env's bound state, the world and the packed image and writes none of it: not a
+ * byte of the env's state and counters, of the weights, of the images, of the replay ring or of
+ * the policy kernels' visiting-order scratch; neither the env's step number nor any counter moves.
+ * Misuse (m, steps or rollout_base negative; epsilon NaN or negative; an unknown mode; a null src,
+ * ret, counted or status with m > 0; act with ld < m, not 16-byte aligned or, for steps > 1, ld
+ * not a multiple of 4) is SE_EINVAL before any launch, whatever the handle's state, and writes
+ * nothing. Then the handle is held to se_policy's readiness: no weights set, or se_set_ports
+ * since they were, is SE_ESTATE. A network and world image that together exceed the LDS are
+ * SE_EINVAL, as for se_policy. m = 0 is a no-op. One launch, no allocation, no synchronisation:
+ * capturable. */
+#define SE_PLAN_RAISED 6    /* a step raised: the rollout ended there, the ship untouched */
+#define SE_QROLL_PAD (-5)   /* an agent index se_step answers with SE_ERR_BAD_INDEX */
+typedef struct se_qnet_out {       /* every pointer may be NULL: not wanted */
+    int32_t *act;                  /* step-major [steps][ld] agent indices; positions not played hold SE_QROLL_PAD */
+    int64_t ld;                    /* >= m, rows 16-byte aligned, a multiple of 4 when steps > 1 */
+    int32_t *explored;             /* m entries: positions that took the explore branch */
+    se_plan_out end;
+} se_qnet_out;
+int se_rollout_qnet(se_qnet* q, int32_t mode /* 0: bf16 as se_policy; 1: fp32-faithful as se_policy_f32 */,
+                    double epsilon, const int32_t* src, int64_t m, const int64_t* ids, int64_t rollout_base,
+                    int32_t steps, double* ret, int32_t* counted, int32_t* status,
+                    const se_qnet_out* out, void* stream);
+
 /* DQN experience replay on the device (agents/dqn.py): remember (:117-123) into a ring of
  * `capacity` transitions (deque(maxlen=memory_size)), and update()'s minibatch (:213-224:
  * random.sample, then the preprocess_state rows as f32). A transition is stored compactly

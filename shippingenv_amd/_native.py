@@ -35,6 +35,9 @@ PLAN_DONE, PLAN_END, PLAN_BAD_SRC = 0, 1, 4
 NAV_INF, NAV_NONE = 0xFFFF, 255
 NAV_OK, NAV_NO_DEST, NAV_UNREACHABLE = 0, 1, 2
 PLAN_STUCK = 5
+# se_rollout_qnet's extra status, and the agent index its action rows pad with
+PLAN_RAISED = 6
+QROLL_PAD = -5
 # se_mcts_choose statuses
 MCTS_OK, MCTS_CUT, MCTS_RAISED, MCTS_NEVER_RETURNS = 0, 1, 2, 3
 MCTS_STUCK = 4  # se_mcts_choose_nav alone
@@ -80,6 +83,11 @@ class SeTableOut(C.Structure):
     """se_table_out: what se_rollout_sarsa writes beside ret, counted and status (NULL: not wanted)."""
     _fields_ = ([(name, C.c_void_p) for name in ("stuck_at", "sample_type", "act_type", "act_a", "act_b")] +
                 [("ld", C.c_int64), ("end", SePlanOut)])
+
+
+class SeQnetOut(C.Structure):
+    """se_qnet_out: what se_rollout_qnet writes beside ret, counted and status (NULL: not wanted)."""
+    _fields_ = [("act", C.c_void_p), ("ld", C.c_int64), ("explored", C.c_void_p), ("end", SePlanOut)]
 
 
 class SeDoneRec(C.Structure):
@@ -134,6 +142,7 @@ SIGNATURES = {
     "se_sarsa_sparse_grow": [_P, _P, _P, _i64, _P],
     "se_sarsa_sparse_home": [_i64, _i64],
     "se_rollout_sarsa": [_P, C.c_double, _P, _i64, _P, _i64, _i32, _P, _P, _P, C.POINTER(SeTableOut), _P],
+    "se_rollout_qnet": [_P, _i32, C.c_double, _P, _i64, _P, _i64, _i32, _P, _P, _P, C.POINTER(SeQnetOut), _P],
     "se_qnet_create": [C.POINTER(_P), _P],
     "se_qnet_set_weights": [_P, _P, _P, _P, _P, _P, _P, _P],
     "se_policy": [_P, _P, C.c_double, _u32, _P, _i64, _P],

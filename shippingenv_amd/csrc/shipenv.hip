@@ -947,7 +947,8 @@ int se_host_destroy(se_host* h) {
 
 // the fused DQN policy step (same translation unit: world image, env handle, Philox)
 #include "qpolicy.h"
-#include "nav.h"   // before mcts.h: se_mcts_choose_nav plays the navigator
+#include "qnet_rollout.h"  // after qpolicy.h: plays its packed image on episode.h's scaffold
+#include "nav.h"  // before mcts.h: se_mcts_choose_nav plays the navigator
 #include "mcts.h"
 #include "sarsa.h"
 #include "sarsa_rollout.h"  // after sarsa.h: plays its tables through sarsa_choose

@@ -461,6 +461,33 @@ class VecDQNAgent:
         """choose_action (agents/dqn.py:177-203) for every env."""
         return self.policy.act(0.0 if deterministic else self.epsilon, self.t, precision=self.precision)
 
+    # ------------------------------------------------------------------ rollouts
+    def rollout(self, src=None, steps=100, epsilon=0.0, ids=None, rollout_base=0, return_end=False,
+                return_actions=False):
+        """QPolicy.rollout with the agent's precision and current weights (the policy's images are
+        rewritten by every update): what the network earns from where the envs stand, on private
+        ship copies. The envs, t, the ring and epsilon are untouched."""
+        return self.policy.rollout(src, steps, epsilon, ids, rollout_base, return_end, return_actions,
+                                   precision=self.precision)
+
+    def evaluate(self, steps=100, ids=None, rollout_base=0):
+        """What the network is worth from where the envs stand -> {start port: mean ret of the
+        greedy (epsilon = 0) rollouts of `steps` positions from the envs whose current origin is
+        that port}; envs without an origin are left out. One launch, the means on the device and
+        one host read; the envs, t, the ring and epsilon are untouched, so it may run in the middle
+        of training (an auto-reset env is only read), and under the same ids it is comparable draw
+        for draw with VecSARSAAgent.evaluate, VecNavigator.rollout and env.rollout."""
+        env, P = self.env, self.env.P
+        ret = self.rollout(None, steps, 0.0, ids, rollout_base).ret
+        origin = env.origin.to(torch.int64)
+        has = (origin >= 0) & (origin < P)  # SE_NONE (255) names no port
+        idx = torch.where(has, origin, torch.zeros_like(origin))
+        acc = torch.zeros((2, P), dtype=torch.float64, device=env.device)
+        acc[0].index_add_(0, idx, torch.where(has, ret, torch.zeros_like(ret)))
+        acc[1].index_add_(0, idx, has.to(torch.float64))
+        s, c = acc.cpu().tolist()
+        return {p: s[p] / c[p] for p in range(P) if c[p] > 0}
+
     def step(self):
         """One training-loop iteration for every env; returns the last update's loss (or None)."""
         # choose_action + remember(state, action): one launch (se_policy_record)

@@ -12,7 +12,9 @@ exploration (choose_action, :177-203) in one launch, without writing Q to HBM.
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -20,6 +22,30 @@ from . import _native as N
 from ._native import _ptr
 
 HIDDEN = 128  # DQNNetwork's hidden_size default (agents/dqn.py:24); the fused kernel's width
+
+
+# se_rollout_qnet's statuses and the agent index its action rows pad with (include/shipenv.h)
+DONE, END, BAD_SRC, RAISED = N.PLAN_DONE, N.PLAN_END, N.PLAN_BAD_SRC, N.PLAN_RAISED
+PAD = N.QROLL_PAD
+
+
+class NetRollout(NamedTuple):
+    """What QPolicy.rollout returns: device tensors of m entries (the ship's six are None
+    without return_end, the action rows None without return_actions)."""
+    ret: torch.Tensor           # f64: the counted steps' rewards summed in order
+    counted: torch.Tensor       # counted steps
+    status: torch.Tensor        # PLAN_DONE / PLAN_END / PLAN_BAD_SRC / PLAN_RAISED
+    explored: torch.Tensor      # positions that took the explore branch
+    raised: torch.Tensor        # raising steps: 1 where the status is PLAN_RAISED, else 0
+    first_err: torch.Tensor     # ERR_* of the raising step, 0 if none
+    first_err_at: torch.Tensor  # its position, -1 if none
+    x: Optional[torch.Tensor] = None
+    y: Optional[torch.Tensor] = None
+    fuel: Optional[torch.Tensor] = None
+    cargo: Optional[torch.Tensor] = None
+    origin: Optional[torch.Tensor] = None
+    dest: Optional[torch.Tensor] = None
+    act: Optional[torch.Tensor] = None  # [steps, m] agent indices, PAD where a position was not played
 
 
 class DQNNetwork(nn.Module):
@@ -94,6 +120,41 @@ class QPolicy:
         N.check(fn(self._h, _ptr(self.actions), float(epsilon), int(t) & 0xFFFFFFFF,
                    _ptr(q_out), ldq, self.env._stream()))
         return self.actions
+
+    def rollout(self, src=None, steps=100, epsilon=0.0, ids=None, rollout_base=0, return_end=False,
+                return_actions=False, precision="bf16"):
+        """Network-policy rollouts (se_rollout_qnet): rollout r plays the packed network, greedy or
+        epsilon-greedy, for `steps` positions on a private copy of env src[r] (int32 [m]; None:
+        every env once), one launch for all positions. The envs, their counters, the weights and
+        the packed images are untouched. ids (int64 [m]) names each rollout's Philox stream
+        instead of rollout_base + r. A step that raises ends the rollout (PLAN_RAISED), as the
+        reference's training loop breaks on one. Position k draws what rollout_plan's position k
+        draws: the rollout equals rollout_plan of the agent indices it emitted (return_actions),
+        and each action is act()'s for an env holding the rollout's ship. precision: "bf16", the
+        network as act() evaluates it; the fp32-faithful rollout ("f32") is not built. Returns a
+        NetRollout of fresh tensors."""
+        if precision not in ("bf16", "f32"):
+            raise ValueError("precision must be 'bf16' or 'f32'")
+        if precision == "f32":
+            raise NotImplementedError("the fp32-faithful rollout is not built: precision='bf16' plays se_policy's network")
+        env = self.env
+        if src is None:
+            src = torch.arange(env.n, dtype=torch.int32, device=env.device)
+        elif not isinstance(src, torch.Tensor):
+            src = torch.as_tensor(np.asarray(src))
+        m, steps = src.numel(), int(steps)
+        s = env._dev(src, torch.int32, count=m)
+        idt = None if ids is None else env._dev(ids, torch.int64, count=m)
+        # own: explored
+        ret, (counted, status), own, noted, end, plan_out = env._episode_outputs(m, return_end, extra=1)
+        act, ld = None, (m + 3) & ~3  # rows 16-byte aligned
+        if return_actions:
+            act = torch.empty((max(steps, 0), ld), dtype=torch.int32, device=env.device)
+        out = N.SeQnetOut(None if act is None else act.data_ptr(), ld, own[0].data_ptr(), plan_out)
+        N.check(N.lib().se_rollout_qnet(self._h, 0, float(epsilon), _ptr(s), m, _ptr(idt), int(rollout_base), steps,
+                                        _ptr(ret), _ptr(counted), _ptr(status), C.byref(out), env._stream()))
+        self._keep = (s, idt)
+        return NetRollout(ret, counted, status, *own, *noted, *end, None if act is None else act[:, :m])
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
