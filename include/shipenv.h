@@ -767,7 +767,17 @@ int se_qnet_set_weights(se_qnet* q, const float* w1, const float* b1, const floa
  * state is only read. Exploration draws
  * Philox(seed, env) at (t, slot 14): word 0 * 2^-32 <= epsilon explores, and word 1
  * picks the k-th valid action (ascending index) uniformly. q_out (optional, NULL):
- * the Q rows as computed, [n][ldq] f32, ldq >= A. */
+ * the Q rows as computed, [n][ldq] f32, ldq >= A.
+ * Non-finite values (se_policy, se_policy_f32 and se_rollout_qnet alike): the greedy action is
+ * the first maximum among the valid rows whose Q compares greater than -inf, so a NaN row
+ * never wins (torch's argmax would return it) and +inf wins over every finite row; an env with
+ * no such row (every valid Q NaN or -inf) plays action 0. q_out shows the NaN / inf of the
+ * weights as computed. A ship whose fuel is not finite as f32 (inf, NaN) has every Q NaN (the
+ * fuel's parts are inf and inf - inf): its q_out row is NaN and it plays action 0 (it still
+ * explores over its valid actions). A finite fuel so large that the activations overflow f32
+ * gives inf / NaN rows as the arithmetic produces them, and the rule above picks among them.
+ * An env's non-finite fuel or Q stays in that env: its neighbours in the tile are computed bit
+ * for bit as without it. */
 int se_policy(se_qnet* q, int32_t* actions, double epsilon, uint32_t t, float* q_out, int64_t ldq,
               void* stream);
 /* Repack from the device weights of the last se_qnet_set_weights (same tensors, new values:
@@ -907,7 +917,15 @@ int se_replay_destroy(se_replay* r);  /* destroy a replay before the env it was 
  * (nn.MSELoss when every w is 1), backward, and one Adam step (torch.optim.Adam, no weight
  * decay) on the online parameters in place. Deterministic: no atomics, fixed summation
  * orders. Parameters: DEVICE f32 tensors of DQNNetwork (hidden 128, torch nn.Linear layout);
- * adam_m / adam_v: zero-initialised tensors of the same shapes (exp_avg, exp_avg_sq). */
+ * adam_m / adam_v: zero-initialised tensors of the same shapes (exp_avg, exp_avg_sq).
+ * Non-finite values: a row without weight (w = 0, or an action outside [0, A), which counts as
+ * w = 0) takes no part whatever it holds: its obs, next_obs, reward and done are not used, so
+ * NaN or inf there leaves the loss, the parameters and the moments bit for bit what they are
+ * with that row zeroed (se_replay_sample writes such rows as zeros; hand-made minibatches need
+ * not). On the rows with weight, non-finite values propagate into the loss and the update as
+ * in the reference, with one deliberate difference: max_a over the target's Q rows skips NaN
+ * (fmaxf), where torch's max returns it. A NaN target row therefore counts as -inf: y is r +
+ * gamma * the largest non-NaN target Q (1 - done), and -inf if every row is NaN. */
 typedef struct se_mlp {
     float* w1; float* b1;  /* fc1 [128][6+4P], [128] */
     float* w2; float* b2;  /* fc2 [128][128], [128] */

@@ -199,7 +199,8 @@ __global__ __launch_bounds__(kQrollBlock) void qnet_rollout_kernel(QrollArgs A) 
             }
             int32_t emitted = SE_QROLL_PAD;
             if (alive) {
-                int act = bidx == 0x7fffffff ? 0 : q.action_of_row(bidx);  // no valid action: 0 (:188-189)
+                // no valid action, or a fuel that is not finite (every Q is NaN then): 0 (:188-189)
+                int act = ((bidx == 0x7fffffff) | !fuel_finite(ff)) ? 0 : q.action_of_row(bidx);
                 if (A.epsilon > 0.0) {
                     const U4 e = draw(L.key, (uint32_t)k, kSlotRolloutQ);
                     if (u32(e.v[0]) <= A.epsilon) {  // np.random.rand() <= epsilon (:191)

@@ -498,12 +498,20 @@ __device__ __forceinline__ void argmax_local_part(const f32x16& c, float& best, 
     }
 }
 
+// A fuel that is not finite (inf or NaN as f32) makes every Q of its env NaN in exact
+// arithmetic (its bf16 parts are inf and inf - inf); the ReLUs here do not keep every NaN
+// (relu_pack is an integer max on the bf16 bits, which sends a NaN with the sign bit set to 0), so
+// the rule is applied where the env's results leave the kernel: its q_out row is NaN and it has
+// no row above -inf, so it plays action 0 (include/shipenv.h).
+__device__ __forceinline__ bool fuel_finite(float ff) { return fabsf(ff) < INFINITY; }
+
 __device__ __forceinline__ void tile_q_out(float* q_out, int64_t ldq, int rows, const f32x16& c, int64_t e, int base,
-                                           int h) {
+                                           int h, float ff) {
+    const bool fin = fuel_finite(ff);
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {  // the full layout: row = action
         const int row = base + 4 * h + (reg & 3) + 8 * (reg >> 2);
-        if (row < rows) q_out[e * ldq + row] = c[reg];
+        if (row < rows) q_out[e * ldq + row] = fin ? c[reg] : NAN;
     }
 }
 
@@ -525,7 +533,8 @@ __device__ __forceinline__ void finish_env(const QnetDims& q, const EnvValid& v,
     }
     if (h == 0 && live) {
         const int P = q.P;
-        int act = bidx == 0x7fffffff ? 0 : q.action_of_row(bidx);  // no valid action: 0 (:188-189)
+        // no valid action, or a fuel that is not finite: 0 (:188-189)
+        int act = ((bidx == 0x7fffffff) | !fuel_finite(ff)) ? 0 : q.action_of_row(bidx);
         if (eps > 0.0) {
             const U4 d = draw(env_key(seed, env_base + e), t, kSlotPolicy);
             if (u32(d.v[0]) <= eps) {  // np.random.rand() <= epsilon (:191)
@@ -867,7 +876,7 @@ void policy_kernel(PolicyArgs A) {
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) {  // the full layout: row = action
                     const int row = base + 4 * h + (reg & 3) + 8 * (reg >> 2);
-                    if (row < q.rows) A.q_out[e * A.ldq + row] = c[reg];
+                    if (row < q.rows) A.q_out[e * A.ldq + row] = fuel_finite(ff) ? c[reg] : NAN;
                 }
             }
         }
@@ -884,7 +893,8 @@ void policy_kernel(PolicyArgs A) {
             bidx = oi;
         }
         if (h == 0 && live) {
-            int act = bidx == 0x7fffffff ? 0 : q.action_of_row(bidx);  // no valid action: 0 (:188-189)
+            // no valid action, or a fuel that is not finite: 0 (:188-189)
+            int act = ((bidx == 0x7fffffff) | !fuel_finite(ff)) ? 0 : q.action_of_row(bidx);
             if (A.eps > 0.0) {
                 const U4 d = draw(env_key(A.seed, A.env_base + e), A.t, kSlotPolicy);
                 if (u32(d.v[0]) <= A.eps) {  // np.random.rand() <= epsilon (:191)
@@ -1532,7 +1542,7 @@ __global__ __launch_bounds__(kPolicyX3Block) void policy_x3_kernel(PolicyArgs A,
         [[maybe_unused]] float best0 = best;
         [[maybe_unused]] int bt = 0;
         uint32_t pm = kQout ? tile_mask(v, 0, P) : 0u, prm = __builtin_amdgcn_readfirstlane(REGM[0]);
-        if (kQout && live) tile_q_out(A.q_out, A.ldq, q.rows, c, e, 0, h);
+        if (kQout && live) tile_q_out(A.q_out, A.ldq, q.rows, c, e, 0, h, ff);
 #pragma nounroll
         for (int mt = 1; mt < q.mt3; ++mt) {
             const int base = mt * 32;
@@ -1566,7 +1576,7 @@ __global__ __launch_bounds__(kPolicyX3Block) void policy_x3_kernel(PolicyArgs A,
             pbase = base;
             if (kQout) pm = tile_mask(v, mt, P);
             prm = __builtin_amdgcn_readfirstlane(REGM[mt]);
-            if (kQout && live) tile_q_out(A.q_out, A.ldq, q.rows, c, e, base, h);
+            if (kQout && live) tile_q_out(A.q_out, A.ldq, q.rows, c, e, base, h, ff);
         }
         X3STAMP(7);
         if (kQout) {

@@ -554,17 +554,17 @@ __global__ __launch_bounds__(kQTBlock) void qtrain_tile_kernel(QtStepArgs A) {
             Pick pk{-1, 0u, 0u, 0.0f, 0.0f, 0.0f, 0, 0};
             const uint32_t t = pt;
             if (row < A.B) pk = pick_resolve(pf, ring, psize, pkey, feistel_half((uint32_t)psize), row, A.B);
-            const bool ok = pk.slot >= 0;
+            // as the sampler's act / weight rows read below: act = ok ? a : 0, weight = ok
+            const int64_t a = row < A.B ? (pk.slot >= 0 ? (int64_t)pk.ac : 0) : -1;
+            const bool live = a >= 0 && a < A.d.A;
+            const bool ok = pk.slot >= 0 && live;  // a row without weight enters as zeros
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
                 X[c * kLS + tid] = c < 6 && ok ? ship_col(pk.sp, pk.sf, c) : 0.0f;
                 XN[c * kLS + tid] = c < 6 && ok ? ship_col(pk.np, pk.nf, c) : 0.0f;
             }
-            // as the sampler's act / weight rows read below: act = ok ? a : 0, weight = ok
-            const int64_t a = row < A.B ? (ok ? (int64_t)pk.ac : 0) : -1;
-            const bool live = a >= 0 && a < A.d.A;
             ACT[tid] = live ? (int)a : 0;
-            WT[tid] = live && ok ? 1.0f : 0.0f;
+            WT[tid] = ok ? 1.0f : 0.0f;
             RW[tid] = ok ? pk.rw : 0.0f;
             DN[tid] = ok && (pk.fl & kRecDone) ? 1.0f : 0.0f;
             if (blockIdx.x == 0 && tid == 0) A.ctr[1] = (int32_t)(t + 1u);  // T2's Adam count
@@ -575,19 +575,30 @@ __global__ __launch_bounds__(kQTBlock) void qtrain_tile_kernel(QtStepArgs A) {
             const int which = e >> 8, c = (e >> 5) & 7, j = e & 31;
             const int64_t row = r0 + j;
             float v = 0.0f;
-            if (c < 6 && row < A.B) v = (which ? A.next_obs : A.obs)[row * in + c];
+            if (c < 6 && row < A.B) {
+                // a row without weight enters as zeros, whatever it holds (0 x inf would
+                // otherwise reach dW1, dW2 and dW3 through h1 and h2): selected, not multiplied
+                // (three independent loads, then one select: no load waits for another)
+                const int64_t a = A.act[row];
+                const float wv = A.weight[row];
+                const float x = (which ? A.next_obs : A.obs)[row * in + c];
+                v = ((a >= 0) & (a < A.d.A) & (wv != 0.0f)) ? x : 0.0f;
+            }
             (which ? XN : X)[c * kLS + j] = v;
         }
         if (tid < 32) {
             // an action outside [0, A) (the reference's gather would raise) takes no part in the
-            // update (weight 0), and its W3 row gather reads row 0 instead of past the matrix
+            // update (weight 0), and its W3 row gather reads row 0 instead of past the matrix;
+            // a row of weight 0 is read as an all-zero row (reward 0, not done)
             const int64_t row = r0 + tid;
             const int64_t a = row < A.B ? A.act[row] : -1;
-            const bool live = a >= 0 && a < A.d.A;
-            ACT[tid] = live ? (int)a : 0;
-            WT[tid] = live ? A.weight[row] : 0.0f;
-            RW[tid] = row < A.B ? A.rew[row] : 0.0f;
-            DN[tid] = row < A.B ? A.done[row] : 0.0f;
+            const bool in_range = a >= 0 && a < A.d.A;
+            const float wt = in_range ? A.weight[row] : 0.0f;
+            const bool live = wt != 0.0f;
+            ACT[tid] = in_range ? (int)a : 0;
+            WT[tid] = wt;
+            RW[tid] = live ? A.rew[row] : 0.0f;
+            DN[tid] = live ? A.done[row] : 0.0f;
         }
     }
     __syncthreads(); QSTAMP(1);
@@ -927,6 +938,8 @@ struct QtAdamArgs {
     int32_t mode;
     float* grad;  // [grad_floats(d)], layout of the Grad offsets below
     int32_t* ctr_sync;  // se_qtrain_step_replay: block 0 sets *ctr_sync = *step_dev (ctr[0] = ctr[1])
+    // 1 - beta and ln(beta) of the betas as decimals (adam_beta below), rounded to f32 once
+    float omb1, omb2, ln_b1, ln_b2;
 };
 
 // The data-parallel gradient: the sums T2 forms before dividing by sum(w), in a flat f32
@@ -959,21 +972,27 @@ __device__ __forceinline__ int row_of_action(const QnetDims& q, int a) {
     return a >= 55 + q.P && r < q.rows ? r : -1;
 }
 
-// torch.optim.Adam (foreach, capturable) for one element: m lerps to g, v = v b2 + (1 - b2) g g,
-// p += m / ((sqrt(v) / sqrt(1 - b2^t) + eps) / (-lr / (1 - b1^t)))
+// torch.optim.Adam (foreach, capturable) for one element: m lerps to g, v lerps to g g,
+// p += m / ((sqrt(v) / sqrt(1 - b2^t) + eps) / (-lr / (1 - b1^t))).
+// The C-ABI takes the betas as f32, and 0.999f is 0.999 (1 + 1.3e-8): formed in f32 from it,
+// 1 - b2 is 1.3e-5 (relative) off, which cancels against 1 - b2^t at t = 1 and, past the warm-up
+// (b2^t -> 0), made every step 6.4e-6 of its length longer than torch.optim.Adam(betas=(0.9,
+// 0.999))'s in float64. So the host takes each beta as the decimal it was written as (adam_beta),
+// and passes 1 - beta and ln(beta) rounded to f32 once; 1 - beta^t = -expm1(t ln beta) has no
+// cancellation at small t, and v = v + (1 - b2)(g g - v) is exact at a steady state, where
+// v b2 + (1 - b2) g g with an f32 b2 is off by the same 1.3e-5.
 struct AdamStep {
-    float b1, b2, eps, step_size, bc2_sqrt;
+    float omb1, omb2, eps, step_size, bc2_sqrt;
     // steps: *A.step_dev, loaded by the caller (no counter in mode 1, which stops before any
     // Adam step)
-    __device__ AdamStep(const QtAdamArgs& A, int32_t steps) : b1(A.beta1), b2(A.beta2), eps(A.eps) {
+    __device__ AdamStep(const QtAdamArgs& A, int32_t steps) : omb1(A.omb1), omb2(A.omb2), eps(A.eps) {
         const float t = A.step_dev ? (float)(steps + (A.bumped ? 0 : 1)) : 1.0f;
-        step_size = 1.0f / ((powf(A.beta1, t) - 1.0f) / A.lr);
-        bc2_sqrt = sqrtf(-(powf(A.beta2, t) - 1.0f));
+        step_size = 1.0f / (expm1f(t * A.ln_b1) / A.lr);
+        bc2_sqrt = sqrtf(-expm1f(t * A.ln_b2));
     }
     __device__ float operator()(float p, float g, float& m, float& v) const {
-        m = m + (1.0f - b1) * (g - m);
-        v = v * b2;
-        v = v + ((1.0f - b2) * g) * g;
+        m = m + omb1 * (g - m);
+        v = v + omb2 * (g * g - v);
         const float denom = ((sqrtf(v) / bc2_sqrt) + eps) / step_size;
         return p + m / denom;
     }
@@ -1560,13 +1579,27 @@ int qtrain_check_qnet(se_qtrain* q, se_qnet* qn) {
     return SE_OK;
 }
 
+// The beta an f32 argument stands for: the shortest decimal that rounds to it (0.999f -> 0.999),
+// as a double; the f32's own value if no decimal of up to 9 digits does (or it is not finite).
+inline double adam_beta(float beta) {
+    char buf[40];
+    for (int digits = 1; digits <= 9; ++digits) {
+        snprintf(buf, sizeof buf, "%.*g", digits, (double)beta);
+        const double d = strtod(buf, nullptr);
+        if ((float)d == beta) return d;
+    }
+    return (double)beta;
+}
+
 QtAdamArgs adam_args(se_qtrain* q, se_qnet* qn, int64_t batch, const int64_t* act, float lr, float beta1,
                      float beta2, float eps, const int32_t* step_dev, float* loss_out, int32_t bumped,
                      int32_t mode, float* grad, int32_t* ctr_sync = nullptr) {
     const int64_t tiles = (batch + kQT - 1) / kQT;
     return QtAdamArgs{q->W, q->on, q->m, q->v, q->d, batch, tiles, act, lr, beta1, beta2, eps, step_dev, loss_out,
                       {qn ? qn->d_img : nullptr, qn ? qn->d_img + qn->c_off : nullptr},
-                      {qn ? qn->q : QnetDims{}, qn ? qn->qc : QnetDims{}}, bumped, mode, grad, ctr_sync};
+                      {qn ? qn->q : QnetDims{}, qn ? qn->qc : QnetDims{}}, bumped, mode, grad, ctr_sync,
+                      (float)(1.0 - adam_beta(beta1)), (float)(1.0 - adam_beta(beta2)), (float)log(adam_beta(beta1)),
+                      (float)log(adam_beta(beta2))};
 }
 
 // T1, then T2 in mode 0 (grad null: sums + Adam) or mode 1 (the sums into grad)

@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import dqn_numeric_support as NS
 import footprint_support as F
 import qnet_rollout_support as QS
 from test_gpu_rollout import load_state
@@ -209,23 +210,28 @@ def test_ids_are_the_streams():
 
 
 # ----------------------------------------------------------------- 2. the policy equality
-def test_every_action_is_se_policy_on_the_ship_before_it(water):
-    """A seeded torch-default-init network on the default world, 67 rollouts of 16 positions from
-    envs after a reset and 30 random steps. For each k, se_rollout_plan of the first k emitted
-    actions gives the ships before position k; loaded into a scratch env, se_policy's greedy action
-    there must equal row k for every rollout still playing. Nothing is left out, no tolerance."""
-    from shippingenv_amd.policy import DQNNetwork, QPolicy
+@pytest.mark.parametrize("family", NS.FAMILIES)
+def test_every_action_is_se_policy_on_the_ship_before_it(water, family):
+    """A seeded network of every family of tests/dqn_numeric_support.py (default: torch's default
+    init) on the default world, 67 rollouts of 8 positions from envs after a reset and 30 random
+    steps, the first 39 of them with the fuels of dqn_numeric_support.FUELS in turn (three rounds:
+    where the bf16 hi + lo split of the fuel changes behaviour). For each k, se_rollout_plan of the
+    first k emitted actions gives the ships before position k; loaded into a scratch env,
+    se_policy's greedy action there must equal row k for every rollout still playing. Nothing is
+    left out, no tolerance."""
+    from shippingenv_amd.policy import QPolicy
     from shippingenv_amd.vec import VecEnv
 
     n = m = 67
-    steps = 16
+    steps = 8
     env = keep(VecEnv(n, seed=0))
     np.testing.assert_array_equal(env.water, water)
     env.reset()
     for t in range(30):
         env.step(env.gen_actions(t))
-    torch.manual_seed(1234)
-    model = DQNNetwork(env.obs_size, env.action_space_size)
+    edge = 3 * len(NS.FUELS)
+    env.fuel[:edge] = torch.as_tensor(np.tile(NS.FUELS, 3), device=env.device)
+    model = NS.make_family(family, env.obs_size, env.action_space_size, seed=1234)
     pol = keep(QPolicy(env, model))
     scratch = keep(VecEnv(n, seed=0))
     spol = keep(QPolicy(scratch, model))
@@ -233,7 +239,7 @@ def test_every_action_is_se_policy_on_the_ship_before_it(water):
     ids = (1 << 33) + 7 * np.arange(m)
     res = pol.rollout(src, steps=steps, epsilon=0.0, ids=ids, return_end=True, return_actions=True)
     got = numpy_result(res)
-    assert_plan_equality(env, src, res, got, ids=ids, what="default init")
+    assert_plan_equality(env, src, res, got, ids=ids, what=family)
     played = got["counted"] + got["raised"]
     compared = 0
     for k in range(steps):
