@@ -4,9 +4,11 @@
 // and the step fused in one position loop, and se_rollout_qnet.
 //
 // A fragment of shipenv.hip's translation unit, included at its end after qpolicy.h: not a
-// stand-alone header. Uses qpolicy.h (QnetDims and the packed compact image, split3, bias_frag,
-// masked_bias, relu_pack, env_valid / tile_maybe / tile_mask, argmax_local_part, the SAME table,
-// se_qnet), rollout.h (drawn_step), env_core.h (decode_agent), episode.h (EpisodeArgs,
+// stand-alone header. Uses qpolicy.h (se_qnet, qnet_ready, resident_grid) and its fragments
+// qnet_image.h (QnetDims and the packed compact image, the SAME table) and qnet_parts.h (split3,
+// obs_frag, bias_frag, masked_bias, relu_pack, env_valid / tile_maybe / tile_mask,
+// argmax_local_part, explore_choice), rollout.h (drawn_step), env_core.h (decode_agent),
+// episode.h (EpisodeArgs,
 // episode_lane, EpisodeTally, episode_store), philox.h and the host side's env_args, fail, HIP_TRY,
 // DeviceGuard, allow_lds, lds_bytes and aligned16.
 //
@@ -54,21 +56,6 @@ struct QrollArgs : EpisodeArgs {
     double epsilon;
     se_qnet_out out;  // null pointers: not wanted
 };
-
-// random.choice(valid_actions) (agents/dqn.py:192) by the word `pick`: the j-th valid action,
-// ascending, as an agent index (policy_kernel's law)
-__device__ __forceinline__ int qroll_choice(const EnvValid& v, int P, uint32_t pick) {
-    const int nsel = __popcll(v.sel);
-    int j = uniform_int(pick, (uint32_t)(4 + nsel + v.cst + v.fst));
-    if (j < 4) return j;
-    if ((j -= 4) < nsel) {  // the j-th port of sel, ascending
-        uint64_t b = v.sel;
-        for (; j > 0; --j) b &= b - 1;
-        return 4 + __builtin_ctzll(b);
-    }
-    j -= nsel;
-    return j < v.cst ? 5 + P + j : 55 + P + (j - v.cst);  // amounts j + 1 (action space)
-}
 
 // The argument block read where it is used, through the kernarg segment (the kernel's one
 // argument lies at its start): the tile's head and its stores read a dozen pointers that the
@@ -131,23 +118,8 @@ __global__ __launch_bounds__(kQrollBlock) void qnet_rollout_kernel(QrollArgs A) 
             const int x = alive ? L.s.x : 0, y = alive ? L.s.y : 0;
             const int origin = L.s.origin == SE_NONE ? -1 : L.s.origin;
             const int dest = L.s.dest == SE_NONE ? -1 : L.s.dest;
-            // the observation row (preprocess_state): torch's .float() of the f64 fuel, as bf16
-            // hi + lo so fc1 sees ~16 bits of it
-            const float ff = (float)L.s.fuel;
-            const __bf16 fh = (__bf16)ff, fl = (__bf16)(ff - (float)fh);
-            bf16x8 ob;
-            ob[0] = (__bf16)(float)L.s.x;
-            ob[1] = (__bf16)(float)L.s.y;
-            ob[2] = fh;
-            ob[3] = fl;
-            ob[4] = fh;
-            ob[5] = fl;
-            ob[6] = (__bf16)(float)origin;
-            ob[7] = (__bf16)(float)dest;
-            if (h) {  // k = 8..10: 1.0 against the bias parts, 11..15 padding
-                ob = bf16x8{};
-                ob[0] = ob[1] = ob[2] = (__bf16)1.0f;
-            }
+            const float ff = (float)L.s.fuel;  // torch's .float() of the f64 fuel
+            const bf16x8 ob = obs_frag(L.s.x, L.s.y, ff, origin, dest, h);
             bf16x8 h1[4][2], h2[4][2];
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {  // fc1 + relu
@@ -190,7 +162,7 @@ __global__ __launch_bounds__(kQrollBlock) void qnet_rollout_kernel(QrollArgs A) 
                 bidx = best != best0 ? mt * 32 + 4 * h + bt : bidx;
             }
             // the two lane halves hold the same rollout: larger value, then lower index (both
-            // halves end with the same winner)
+            // halves end with the same winner; merge_halves, inline: the call moved this kernel's registers)
             const float ob2 = __shfl_xor(best, 32);
             const int oi = __shfl_xor(bidx, 32);
             if (ob2 > best || (ob2 == best && oi < bidx)) {
@@ -204,7 +176,7 @@ __global__ __launch_bounds__(kQrollBlock) void qnet_rollout_kernel(QrollArgs A) 
                 if (A.epsilon > 0.0) {
                     const U4 e = draw(L.key, (uint32_t)k, kSlotRolloutQ);
                     if (u32(e.v[0]) <= A.epsilon) {  // np.random.rand() <= epsilon (:191)
-                        act = qroll_choice(v, P, e.v[1]);
+                        act = explore_choice(v.sel, v.cst, v.fst, P, e.v[1]);
                         explored += 1;
                     }
                 }
@@ -251,13 +223,9 @@ int se_rollout_qnet(se_qnet* qn, int32_t mode, double epsilon, const int32_t* sr
             return fail(SE_EINVAL, "action rows must be 16-byte aligned (row stride a multiple of 4)");
     }
     // then the handle, held to se_policy's readiness
-    if (!qn) return fail(SE_EINVAL, "null qnet");
-    se_env* env = qn->env;
-    int rc = check_ready(env);
+    int rc = qnet_ready(qn);
     if (rc) return rc;
-    if (!qn->packed) return fail(SE_ESTATE, "se_qnet_set_weights has not been called");
-    if (qn->world_version != env->world_version)
-        return fail(SE_ESTATE, "ports changed since se_qnet_set_weights (the port block is folded into fc1)");
+    se_env* env = qn->env;
     if (m == 0) return SE_OK;
     const QnetDims& q = qn->qc;  // the compact layout: only the actions some env can ever take
     const size_t lds = (size_t)q.bytes() + lds_bytes(env);
@@ -273,9 +241,7 @@ int se_rollout_qnet(se_qnet* qn, int32_t mode, double epsilon, const int32_t* sr
     A.epsilon = epsilon;
     if (out) A.out = *out;
     // one workgroup per CU stays resident; its waves take the tiles in a grid-stride loop
-    const int64_t tiles = (m + 31) / 32;
-    const int64_t want = (tiles + kQrollWaves - 1) / kQrollWaves;
-    const int grid = (int)(want < qn->cus ? want : qn->cus);
+    const int grid = resident_grid(m, kQrollWaves, qn->cus);
     qnet_rollout_kernel<<<grid, kQrollBlock, lds, (hipStream_t)stream>>>(A);
     HIP_TRY(hipGetLastError());
     return SE_OK;

@@ -5,8 +5,9 @@
 //
 // A fragment of shipenv.hip's translation unit, included at its end after replay.h:
 // not a stand-alone header. Uses world.h (WorldDims, LdsWorld, world_view),
-// env_core.h (env_key), step_io.h (kRecDone), qpolicy.h (se_qnet, QnetDims, the bf16
-// split and MFMA helpers), replay.h (se_replay, Ring, the pick_* sampler, ship_col),
+// env_core.h (env_key), step_io.h (kRecDone), qpolicy.h (se_qnet) and its fragments
+// qnet_image.h (QnetDims, acc_row) and qnet_parts.h (the bf16 split and MFMA helpers: split3,
+// relu_split3, mfma_bf16, khalf_x3), replay.h (se_replay, Ring, the pick_* sampler, ship_col),
 // and the host side's se_env, check_ready, fail, HIP_TRY, DeviceGuard and
 // allow_lds (host.h).
 //
@@ -17,7 +18,7 @@
 // The torch version is about 50 small kernels per update, launch-bound below B = 2^13.
 // Here it is two kernels, all in f32 arithmetic, deterministic (fixed summation orders, no
 // atomics). The forward GEMMs (fc2 of both nets, the target's fc3) run on bf16 MFMA with
-// every f32 operand split into three bf16 parts (x3_index, below); fc1 and the
+// every f32 operand split into three bf16 parts (x3w_index, below); fc1 and the
 // backward on v_mfma_f32_32x32x2_f32 (an exact f32 fma chain; gfx950 has no xf32):
 //
 // T1, qtrain_tile_kernel (one workgroup per 32 samples, 8 waves: the online and the
@@ -101,7 +102,6 @@ struct QtWork {
     int64_t slot_ld;
 };
 
-__device__ __forceinline__ void st_part(float* p, float v) { *p = v; }
 // T1's dW2 / dW3 partials as 16-byte stores (4 consecutive f1 / feature columns of one
 // row: the MFMAs take H1 / H2 as their A operand, so a lane's accumulator registers 4q..4q+3
 // are 4 adjacent columns), write-through (buffer-store aux 16 = sc1), so the 12.6-16.8 MB of
@@ -192,11 +192,11 @@ __device__ __forceinline__ void store_relu(float* dst, int tile, const f32x16& a
 }
 
 // T1's forward GEMMs (fc2 of both nets, the target's fc3) on v_mfma_f32_32x32x16_bf16 with
-// every f32 operand split into three bf16 parts (split3 in qpolicy.h: round to nearest, exact
+// every f32 operand split into three bf16 parts (split3 in qnet_parts.h: round to nearest, exact
 // remainders) and the six part products of order <= 2, smallest first: the policy's
 // fp32-faithful datapath (§10), at 6 x 32 MFMA cycles per K = 16 where the f32 MFMA takes
 // 8 x 64. fc2 / fc3's weights are stored pre-split in global memory (three bf16 parts,
-// [tile][k-step][part][lane] bf16x8, kstep_x3's layout; 6 B per weight instead of 4), so T1
+// [tile][k-step][part][lane] bf16x8, x3_frags' layout; 6 B per weight instead of 4), so T1
 // runs no weight splits; the activations are split once, by the wave that produced them, into
 // LDS B fragments. The backward stays on f32 MFMA: split-bf16 backward forms measured slower
 // (dH1 / dW2 / dW3 split in registers: update 38.8 -> 41.1 us, profiles/r05/ab_update_x3_backward.jsonl;
@@ -206,17 +206,10 @@ __device__ __forceinline__ void store_relu(float* dst, int tile, const f32x16& a
 // coalesced 256-byte row of it instead of scanning every tile's 32-entry slot map (9.4 MB of
 // map lines across the W3 blocks at B = 8192); 0: the scan
 
-// f32 image index of W[row][k] (128 columns) for the split-bf16 A operand: [row tile][k-step
-// g][lane][8], element j of lane (r, h) = W[32 tile + r][32 (g >> 1) + acc_row(g & 1, j, h)],
+// bf16 index of part 0 of W[row][k] (128 columns) in a pre-split image: [row tile][k-step g]
+// [part][lane][8], element j of lane (r, h) = W[32 tile + r][32 (g >> 1) + acc_row(g & 1, j, h)],
 // the column order in which a 32 x 32 accumulator's registers 8s..8s+7 are the B fragment of
-// k-step s (qnet_pack_kernel's acc_row)
-__host__ __device__ __forceinline__ int x3_index(int row, int k) {
-    const int kk = k & 31, g = 2 * (k >> 5) + (kk >> 4), h = (kk >> 2) & 1, j = 4 * ((kk >> 3) & 1) + (kk & 3);
-    return (((row >> 5) * 8 + g) * 64 + (row & 31) + 32 * h) * 8 + j;
-}
-
-// bf16 index of part 0 of W[row][k] in a pre-split image: [row tile][k-step g]
-// [part][lane][8], elements as x3_index; part p is 512 p further
+// k-step s (qnet_image.h's acc_row); part p is 512 p further
 __host__ __device__ __forceinline__ int x3w_index(int row, int k) {
     const int kk = k & 31, g = 2 * (k >> 5) + (kk >> 4), h = (kk >> 2) & 1, j = 4 * ((kk >> 3) & 1) + (kk & 3);
     return (((row >> 5) * 8 + g) * 3 * 64 + (row & 31) + 32 * h) * 8 + j;
@@ -235,94 +228,13 @@ __device__ __forceinline__ f32x16 gemm_x3w(const bf16x8 (*w)[3], const bf16x8* S
         if (i + 1 < G)
 #pragma unroll
             for (int p = 0; p < 3; ++p) x[n][p] = S[((g0 + i + 1) * 3 + p) * 64 + lane];
-        acc = mfma_bf16(w[i][0], x[c][2], acc);
-        acc = mfma_bf16(w[i][1], x[c][1], acc);
-        acc = mfma_bf16(w[i][2], x[c][0], acc);
-        acc = mfma_bf16(w[i][0], x[c][1], acc);
-        acc = mfma_bf16(w[i][1], x[c][0], acc);
-        acc = mfma_bf16(w[i][0], x[c][0], acc);
-    }
-    return acc;
-}
-
-// parts p0 .. p1 - 1 of eight f32 weights (a, b) -> their bf16 splits w[0..2] (split3)
-__device__ __forceinline__ void split8_half(const float4& a, const float4& b, bf16x8 (&w)[3], int half) {
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int q = 2 * half; q < 2 * half + 2; ++q) {
-        const f32x2 x{v[2 * q], v[2 * q + 1]};
-        const bf16x2 p0 = __builtin_convertvector(x, bf16x2);
-        const f32x2 r1 = sub2(x, __builtin_convertvector(p0, f32x2));
-        const bf16x2 p1 = __builtin_convertvector(r1, bf16x2);
-        const bf16x2 p2 = __builtin_convertvector(sub2(r1, __builtin_convertvector(p1, f32x2)), bf16x2);
-        w[0][2 * q] = p0[0];
-        w[0][2 * q + 1] = p0[1];
-        w[1][2 * q] = p1[0];
-        w[1][2 * q + 1] = p1[1];
-        w[2][2 * q] = p2[0];
-        w[2][2 * q + 1] = p2[1];
-    }
-}
-
-// sample-major split tiles: [part][feature][32 samples] bf16, 64-byte rows of four 16-byte chunks
-// (8 samples each), chunk k of row r stored at chunk slot k ^ ((r >> 2) & 3), so that 16
-// consecutive rows' chunk k (one 16-lane pass of a fragment read) fall in 16 distinct bank groups
-__device__ __forceinline__ int tslot(int row, int chunk) { return row * 4 + (chunk ^ ((row >> 2) & 3)); }
-constexpr int kTS = 32;
-// eight f32 values -> their three bf16 parts, stored as chunk slot `slot` of the three parts'
-// sample-major split tiles (parts 128 x 32 elements apart)
-__device__ __forceinline__ void t_split8(const float (&v)[8], __bf16* T, int slot) {
-    __bf16* dst = T + 8 * slot;
-    bf16x8 w[3];
-    const float4 x = make_float4(v[0], v[1], v[2], v[3]), y = make_float4(v[4], v[5], v[6], v[7]);
-    split8_half(x, y, w, 0);
-    split8_half(x, y, w, 1);
-#pragma unroll
-    for (int p = 0; p < 3; ++p) *reinterpret_cast<bf16x8*>(dst + p * 128 * kTS) = w[p];
-}
-// the same from eight consecutive floats of an f32 LDS tile row
-__device__ __forceinline__ void t_split_row(const float* src, __bf16* T, int slot) {
-    float v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = src[i];
-    t_split8(v, T, slot);
-}
-
-// acc + W X over k-steps [g0, g0 + G): W from f32 registers wa[2 (g - g0)], [2 (g - g0) + 1]
-// (split here), X the LDS B fragments S[g][part][lane]. Step g + 1's splits and LDS reads are
-// issued between step g's MFMAs (sched_barrier fences: left alone the scheduler
-// clustered the VALU ahead of the chain, as in the policy's x3 kernel).
-template <int G>
-__device__ __forceinline__ f32x16 gemm_x3(const float4* wa, const bf16x8* S, int g0, f32x16 acc, int lane) {
-    bf16x8 w[2][3], x[2][3];
-    split8_half(wa[0], wa[1], w[0], 0);
-    split8_half(wa[0], wa[1], w[0], 1);
-#pragma unroll
-    for (int p = 0; p < 3; ++p) x[0][p] = S[(g0 * 3 + p) * 64 + lane];
-#pragma unroll
-    for (int i = 0; i < G; ++i) {
-        const int c = i & 1, n = c ^ 1;
-        if (i + 1 < G)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) x[n][p] = S[((g0 + i + 1) * 3 + p) * 64 + lane];
-        acc = mfma_bf16(w[c][0], x[c][2], acc);
-        acc = mfma_bf16(w[c][1], x[c][1], acc);
-        acc = mfma_bf16(w[c][2], x[c][0], acc);
-        __builtin_amdgcn_sched_barrier(0);
-        if (i + 1 < G) split8_half(wa[2 * i + 2], wa[2 * i + 3], w[n], 0);
-        __builtin_amdgcn_sched_barrier(0);
-        acc = mfma_bf16(w[c][0], x[c][1], acc);
-        acc = mfma_bf16(w[c][1], x[c][0], acc);
-        acc = mfma_bf16(w[c][0], x[c][0], acc);
-        __builtin_amdgcn_sched_barrier(0);
-        if (i + 1 < G) split8_half(wa[2 * i + 2], wa[2 * i + 3], w[n], 1);
-        __builtin_amdgcn_sched_barrier(0);
+        acc = khalf_x3(w[i], x[c], khalf_x3(w[i], x[c], acc, 0), 1);  // the six part products
     }
     return acc;
 }
 
 // relu of a 32-row accumulator tile `tile` of a layer's output, split into the LDS B
-// fragments of k-steps 2 tile, 2 tile + 1 (each lane its own slots: see x3_index)
+// fragments of k-steps 2 tile, 2 tile + 1 (each lane its own slots: see x3w_index)
 __device__ __forceinline__ void store_split(bf16x8* S, int tile, const f32x16& acc, int lane) {
     bf16x8 sp[2][3];
     relu_split3(acc, sp);
@@ -643,12 +555,7 @@ __global__ __launch_bounds__(kQTBlock) void qtrain_tile_kernel(QtStepArgs A) {
             if (g + 1 < 8)
 #pragma unroll
                 for (int q = 0; q < 3; ++q) x[c ^ 1][q] = S[((g + 1) * 3 + q) * 64 + lane];
-            acc = mfma_bf16(wa[g][0], x[c][2], acc);
-            acc = mfma_bf16(wa[g][1], x[c][1], acc);
-            acc = mfma_bf16(wa[g][2], x[c][0], acc);
-            acc = mfma_bf16(wa[g][0], x[c][1], acc);
-            acc = mfma_bf16(wa[g][1], x[c][0], acc);
-            acc = mfma_bf16(wa[g][0], x[c][0], acc);
+            acc = khalf_x3(wa[g], x[c], khalf_x3(wa[g], x[c], acc, 0), 1);  // the six part products
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int q = 0; q < 3; ++q) wb[g][q] = P3[(g * 3 + q) * 64 + lane];
@@ -1164,8 +1071,6 @@ __device__ __forceinline__ float slot_row_sum(const float* w3, const float* b3, 
     __syncthreads();  // red and list may be reused
     return r;
 }
-
-__device__ __forceinline__ float comp(const float4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
 
 // Workgroups: [0, 128) W1 row f (+ b1, the fold, the loss at f = 0); [128, 384) W2 64-element
 // blocks (+ b2 on a row's first block); then mt3 x 32 W3 rows in two halves (+ b3 of the row).

@@ -1,4 +1,4 @@
-"""Register / spill summary of the policy and update kernels (compile only, no GPU):
+"""Register / spill summary of the policy, network-rollout and update kernels (compile only, no GPU):
 
     python tools/kres.py [extra hipcc flags, e.g. -DSHIPENV_X3P=0]
 """
@@ -21,7 +21,7 @@ for line in out.splitlines():
     if m and cur:
         rows[cur][m.group(1).split(" [")[0]] = int(m.group(2))
 for k, v in rows.items():
-    if "policy" in k or "qtrain" in k:
+    if "policy" in k or "qtrain" in k or "qnet_rollout" in k:
         name = re.sub(r"^_ZN12_GLOBAL__N_1\d+", "", k)[:60]
         print(f"{name:60s} vgpr {v.get('VGPRs')} sgpr {v.get('TotalSGPRs')} vspill {v.get('VGPRs Spill')} "
               f"sspill {v.get('SGPRs Spill')} scratch {v.get('ScratchSize')} waves {v.get('Occupancy')}")
